@@ -8,10 +8,16 @@ squares are independent, each rank extends its own batch (weak scaling, no
 data-path collective); the barrier + max-over-ranks timing follows the driver
 contract.
 
-Also reported: RS GB/s (algorithmic bytes 4k^2*512 per square over the RS
-kernels' time), NMT SHA-256 compressions/s (983,550 per k=128 square, each
-leaf hashed once), the roofline of the dominant kernel measured with HIP
-events on the launch stream, and the CPU oracle ("port") on host cores.
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N
+steps and prints the headline line; `--dump-outputs DIR` also writes what the
+last timed step computed as DIR/<name>.npy.
+
+With `--full`, also reported: RS GB/s (algorithmic bytes 4k^2*512 per square
+over the RS kernels' time), NMT SHA-256 compressions/s (983,550 per k=128
+square, each leaf hashed once), the roofline of the dominant kernel measured
+with HIP events on the launch stream, the headline bit-exact check, the block
+replay, the end-to-end and other-config lines, and the CPU oracle ("port") on
+host cores.
 """
 import argparse
 import json
@@ -330,6 +336,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: bit-exact check, per-kernel times and roofline, block replay, "
+                         "end-to-end, the other configs and the CPU baseline (each has its own --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (roots, DAHs, status, a seeded sample of EDS "
+                         "shares) as DIR/<name>.npy, float32 (headline mode, rank 0)")
     ap.add_argument("--k", type=int, default=128)
     ap.add_argument("--batch", type=int, default=256,
                     help="squares per GPU per step (SURVEY.md §8d: C2 batches of >= 256 squares)")
@@ -362,6 +374,8 @@ def main():
     ap.add_argument("--replay-dump", default=None,
                     help="write the sampled replay DAHs (block -> hex) to this JSON file (tests)")
     args = ap.parse_args()
+    if args.dump_outputs and args.mode != "extend":
+        ap.error("--dump-outputs applies to the headline (--mode extend)")
     if args.mode == "split":
         return bench_split_main(args)
     if args.mode == "mixed":
@@ -386,7 +400,7 @@ def main():
     # up to the batch size if --distinct is smaller
     nd = min(args.distinct, B)
     host = synth.blob_squares(k, HEADLINE_SEED, rank * B, nd, threads=host_threads())
-    batch_ods = np.stack([host[i % nd] for i in range(B)])
+    batch_ods = host if nd == B else np.stack([host[i % nd] for i in range(B)])
     ds.load_ods(batch_ods)
     torch.cuda.synchronize()
 
@@ -410,6 +424,45 @@ def main():
     barrier(dist)
     el = time.perf_counter() - t0
     el_max = max_over_ranks(dist, el, local)
+    squares = B * args.steps * world
+    value = squares / el_max
+    ms_step = el_max / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ds)
+
+    out = {
+        "metric": "EDS+DAH squares/sec (128→256 sq, node) + RS GB/s & NMT SHA-256 hashes/sec",
+        "value": value,
+        "unit": "squares/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_step,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": "synthetic random-namespace blob shares (sorted, seeded), device-resident",
+        "config": {
+            "workload": f"{k}x{k} ODS -> {2*k}x{2*k} EDS + NMT row/col roots + DAH (configs[1])",
+            "k": k,
+            "squares_per_gpu_per_step": B,
+            "global_batch": B * world,
+            "parallelism": f"squares sharded over {world} GPU(s), no collective",
+            "ods_layout": "in place (Q0 of the EDS buffer)" if args.in_place else "separate ODS buffer",
+        },
+    }
+    if not args.full:  # a plain run: the headline alone
+        st = ds.status.cpu().numpy()
+        if (st != 0).any():
+            raise SystemExit(f"rank {rank}: status error {st}")
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        ctx.close()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
     rank_ms = per_rank_ms(dist, world, el_own / args.steps * 1e3)
     # the timed batch proves its own output before anything else runs on it
     headline_check = (check_headline(dist, local, ctx, ds, batch_ods) if args.check
@@ -431,10 +484,6 @@ def main():
     st = ds.status.cpu().numpy()
     if (st != 0).any():
         raise SystemExit(f"rank {rank}: status error {st}")
-
-    squares = B * args.steps * world
-    value = squares / el_max
-    ms_step = el_max / args.steps * 1e3
 
     # mean per launch of each kernel id; one launch of each per step except the
     # trees (one launch sequence per step, summed by the library per scope)
@@ -468,27 +517,7 @@ def main():
                               "headline step, per launch, tagged with the build they came from")
     roof["avg_launch_ms"] = per[dom]
 
-    out = {
-        "metric": "EDS+DAH squares/sec (128→256 sq, node) + RS GB/s & NMT SHA-256 hashes/sec",
-        "value": value,
-        "unit": "squares/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_step,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "u8",
-        "data": "synthetic random-namespace blob shares (sorted, seeded), device-resident",
-        "config": {
-            "workload": f"{k}x{k} ODS -> {2*k}x{2*k} EDS + NMT row/col roots + DAH (configs[1])",
-            "k": k,
-            "squares_per_gpu_per_step": B,
-            "global_batch": B * world,
-            "parallelism": f"squares sharded over {world} GPU(s), no collective",
-            "ods_layout": "in place (Q0 of the EDS buffer)" if args.in_place else "separate ODS buffer",
-        },
+    out.update({
         "rs_gbs": rs_gbs,
         "nmt_sha256_compressions_per_s": comp_per_s,
         "kernel_ms_per_step": {n: per[n] for n in per if per[n]},
@@ -498,7 +527,7 @@ def main():
         "valu_issue": valu_issue(k, B, ms_step, per["nmt_leaves"]),
         "headline_bit_exact": headline_check["bit_exact"],
         "headline_check": headline_check,
-    }
+    })
     # single-square latency first: after the replay's 64 GiB page-locked
     # allocation the same device->host copies ran slower (k=128 with the EDS
     # returned: 1.40 vs 0.89 ms, profiles/single_square_r02.log)
@@ -561,6 +590,37 @@ def main():
     ctx.close()
     if dist is not None:
         dist.destroy_process_group()
+
+
+DUMP_SEED = 0xD0A7
+# rows kept per dumped array (float32): 2 x 65536 x 90 roots + 16384 x (32 + 1)
+# + 4096 x 512 EDS bytes = 57.7 MB, under the 64 MB a dump may take
+DUMP_ROWS = {"row_roots": 65536, "col_roots": 65536, "dah": 16384, "status": 16384, "eds_sample": 4096}
+
+
+def _dump_rows(t, max_rows: int, seed: int):
+    """Rows of the 2-D tensor `t` as float32: all of them, or a sorted seeded
+    sample of `max_rows` (the same rows for the same shape, run after run)."""
+    n = int(t.shape[0])
+    if n > max_rows:
+        idx = np.sort(np.random.default_rng(seed).choice(n, max_rows, replace=False))
+        t = t[torch.from_numpy(idx).to(t.device)]
+    return t.cpu().numpy().astype(np.float32)
+
+
+def dump_outputs(path: str, ds) -> None:
+    """--dump-outputs: what the last timed step left in the caller's buffers of
+    dagpu_extend_batch_device -- every row/column root, DAH and status of the
+    batch (a seeded sample of squares' rows past DUMP_ROWS) and a seeded sample
+    of 512-byte EDS shares (the whole EDS is 32 MiB per k = 128 square) -- as
+    <path>/<name>.npy, bytes as float32.  Called after the synchronise that
+    ends the timed region."""
+    os.makedirs(path, exist_ok=True)
+    w = 2 * ds.k
+    arrays = {"row_roots": ds.row_roots.view(ds.n * w, -1), "col_roots": ds.col_roots.view(ds.n * w, -1),
+              "dah": ds.dah, "status": ds.status.view(ds.n, 1), "eds_sample": ds.eds.view(ds.n * w * w, SHARE)}
+    for i, (name, t) in enumerate(arrays.items()):
+        np.save(os.path.join(path, name + ".npy"), _dump_rows(t, DUMP_ROWS[name], DUMP_SEED + i))
 
 
 def check_headline(dist, local, ctx, ds, batch_ods):

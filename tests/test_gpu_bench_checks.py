@@ -95,8 +95,8 @@ def _run_bench(args, corrupt=None, timeout=110, nccl=False):
     return subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=timeout)
 
 
-_REPLAY = ["--steps", "2", "--warmup", "1", "--batch", "8", "--replay-blocks", "40", "--no-cpu",
-           "--no-split"]
+_REPLAY = ["--full", "--steps", "2", "--warmup", "1", "--batch", "8", "--replay-blocks", "40",
+           "--no-cpu", "--no-split"]
 
 
 def test_replay_rehearsal_two_ranks(tmp_path):
@@ -138,8 +138,8 @@ def test_rccl_path_one_rank(tmp_path):
     replay's all-gathers and max-reduces and the split square's all-to-all and
     all-gathers run through RCCL (torch backend "nccl"); outputs bit-exact."""
     dump = str(tmp_path / "replay.json")
-    out = _run_bench(["--steps", "2", "--warmup", "1", "--batch", "8", "--replay-blocks", "24", "--no-cpu",
-                      "--split-k", "16", "256", "--split-steps", "1", "--replay-dump", dump], nccl=True)
+    out = _run_bench(["--full", "--steps", "2", "--warmup", "1", "--batch", "8", "--replay-blocks", "24",
+                      "--no-cpu", "--split-k", "16", "256", "--split-steps", "1", "--replay-dump", dump], nccl=True)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads([x for x in out.stdout.splitlines() if x.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["block_replay"]["bit_exact"] is True
@@ -314,8 +314,46 @@ def test_two_threads_pipelined(ctx):
 def test_headline_check_fatal():
     """bench.py's headline bit-exact check fires on a corrupted DAH."""
     env = dict(os.environ, DAGPU_BENCH_CORRUPT="headline")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1",
                           "--batch", "64", "--no-cpu", "--no-replay", "--no-e2e", "--no-configs"],
                          env=env, cwd=ROOT, capture_output=True, text=True, timeout=110)
     assert out.returncode != 0
     assert "FATAL: headline bit-exact check (1 DAHs" in out.stderr, out.stderr[-2000:]
+
+
+def test_plain_run_dumps_outputs(tmp_path):
+    """A plain run prints the headline line alone (nothing of --full) with
+    exactly --steps timed steps, and --dump-outputs writes the last step's
+    roots, DAHs and status and a seeded sample of EDS shares as float32: equal
+    to the oracle's for the same seeded squares."""
+    import bench
+
+    k, n = 16, 5
+    dump = tmp_path / "dump"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3",
+                          "--warmup", "1", "--k", str(k), "--batch", str(n), "--dump-outputs", str(dump)],
+                         cwd=ROOT, capture_output=True, text=True, timeout=110)
+    assert out.returncode == 0, out.stderr[-3000:]
+    line = json.loads([x for x in out.stdout.splitlines() if x.startswith("{")][-1])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["unit"] == "squares/s" and line["dtype"] == "u8"
+    assert line["higher_is_better"] is True and line["ms_per_step"] > 0
+    assert abs(line["value"] - n / (line["ms_per_step"] * 1e-3)) <= 1e-6 * line["value"]
+    for key in ("headline_check", "kernel_ms_per_step", "roofline", "block_replay", "end_to_end", "other_configs",
+                "cpu_baseline"):
+        assert key not in line, key
+    got = {f[:-4]: np.load(dump / f) for f in sorted(os.listdir(dump))}
+    assert sorted(got) == ["col_roots", "dah", "eds_sample", "row_roots", "status"]
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64e6
+    w = 2 * k
+    ods = synth.blob_squares(k, bench.HEADLINE_SEED, 0, n)
+    want = [oracle.extend_and_dah(ods[i].reshape(k * k, 512), k) for i in range(n)]
+    assert (got["status"] == 0).all() and got["status"].shape == (n, 1)
+    assert (got["dah"] == np.stack([np.frombuffer(x[3], np.uint8) for x in want])).all()
+    assert (got["row_roots"] == np.concatenate([x[1].reshape(w, 90) for x in want])).all()
+    assert (got["col_roots"] == np.concatenate([x[2].reshape(w, 90) for x in want])).all()
+    # n * w * w = 5120 shares, of which a sorted seeded sample of 4096 is kept
+    eds = np.concatenate([np.asarray(x[0]).reshape(w * w, 512) for x in want])
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED + 4).choice(n * w * w, bench.DUMP_ROWS["eds_sample"],
+                                                                    replace=False))
+    assert got["eds_sample"].shape == (4096, 512) and (got["eds_sample"] == eds[idx]).all()

@@ -18,7 +18,7 @@ while [ $# -gt 0 ]; do
 done
 wl=$1; shift
 case $wl in
-  headline) args="--steps 20 --warmup 3 --no-cpu --no-replay --no-e2e --no-configs";;
+  headline) args="--full --steps 20 --warmup 3 --no-cpu --no-replay --no-e2e --no-configs";;
   repair128) args="--mode repair --k 128 --batch 256 --steps 5 --warmup 1";;
   repair512) args="--mode repair --k 512 --batch 2 --steps 5 --warmup 1";;
   repair512q3) args="--mode repair --k 512 --batch 2 --steps 5 --warmup 1 --pattern q3";;

@@ -6,7 +6,7 @@ OUT=gpurun_out/round; mkdir -p $OUT
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 150 --timeout-method thread > $OUT/gpu_tests.log 2>&1
 rc=$?; echo "tests rc=$rc"; tail -2 $OUT/gpu_tests.log
 [ $rc -ne 0 ] && { grep -E "FAILED|Error" $OUT/gpu_tests.log | head; exit $rc; }
-timeout -k 10 500 python -u bench.py > $OUT/bench_full.log 2>&1 || { echo "bench failed"; tail -5 $OUT/bench_full.log; exit 1; }
+timeout -k 10 500 python -u bench.py --full > $OUT/bench_full.log 2>&1 || { echo "bench failed"; tail -5 $OUT/bench_full.log; exit 1; }
 echo "bench ok"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_repair -o run -- python3 bench.py --mode repair --steps 3 > $OUT/trace_repair.log 2>&1 || { echo "repair trace failed"; tail -5 $OUT/trace_repair.log; exit 1; }
 echo "repair trace ok"

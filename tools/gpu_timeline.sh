@@ -4,7 +4,7 @@
 set -o pipefail
 cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/tl; mkdir -p $OUT
-BENCH="bench.py --steps 3 --warmup 1 --no-cpu --no-e2e --no-replay --no-configs --distinct 16"
+BENCH="bench.py --full --steps 3 --warmup 1 --no-cpu --no-e2e --no-replay --no-configs --distinct 16"
 for spec in "$@"; do
   label=${spec%%:*}; envs=${spec#*:}
   env $envs timeout -k 10 200 rocprofv3 --kernel-trace --output-format csv -d $OUT/$label -o run -- python3 $BENCH > $OUT/$label.log 2>&1 || { echo "$label failed"; tail -20 $OUT/$label.log; exit 1; }
