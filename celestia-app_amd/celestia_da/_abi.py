@@ -42,6 +42,10 @@ EXPORTS = (
     "dagpu_last_error",
     "dagpu_nmt_verify_inclusion",
     "dagpu_merkle_verify",
+    "dagpu_nmt_verify_batch",
+    "dagpu_nmt_verify_workspace_size",
+    "dagpu_nmt_verify_batch_device",
+    "dagpu_merkle_verify_batch",
     "dagpu_host_alloc",
     "dagpu_host_free",
     "dagpu_host_register",
@@ -156,6 +160,11 @@ def lib() -> ctypes.CDLL:
         i64 = ctypes.c_int64
         L.dagpu_nmt_verify_inclusion.argtypes = [vp, vp, sz, sz, i64, i64, vp, sz, vp]
         L.dagpu_merkle_verify.argtypes = [vp, vp, sz, i64, i64, vp, sz]
+        L.dagpu_nmt_verify_batch.argtypes = [vp, sz, vp, vp, sz, vp, sz, sz, vp, sz, vp, sz, vp]
+        L.dagpu_nmt_verify_workspace_size.argtypes = [sz, sz]
+        L.dagpu_nmt_verify_workspace_size.restype = sz
+        L.dagpu_nmt_verify_batch_device.argtypes = [vp, sz, vp, vp, sz, vp, sz, sz, vp, sz, vp, sz, vp, vp, vp]
+        L.dagpu_merkle_verify_batch.argtypes = [vp, sz, vp, vp, sz, sz, vp, vp, sz, vp, sz, vp]
         L.dagpu_host_alloc.argtypes = [sz]
         L.dagpu_host_alloc.restype = vp
         L.dagpu_host_free.argtypes = [vp]

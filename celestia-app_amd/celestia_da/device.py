@@ -21,6 +21,45 @@ def _stream_handle(stream: Optional[torch.cuda.Stream]) -> int:
     return int(s.cuda_stream)
 
 
+def nmt_verify_batch_device(desc, namespaces: torch.Tensor, leaves: torch.Tensor, leaf_len: int,
+                            nodes: torch.Tensor, roots: torch.Tensor, ctx: Optional[Context] = None,
+                            stream: Optional[torch.cuda.Stream] = None,
+                            workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dagpu_nmt_verify_batch_device: many nmt inclusion proofs against data
+    already in HBM; returns the (n,) int32 status tensor on the device (0 or
+    ERR_PROOF per proof), enqueued on `stream` (no sync of the results).
+
+    desc: (n, 8) int64 on the HOST (proof.PackedNMT.desc); namespaces (29 B
+    each), leaves (leaf_len bytes each), nodes and roots (90 B each): uint8
+    tensors on one device.  With leaf_len == 512 `leaves` may be an extended
+    square itself (cell (r, c) = leaf r * 2k + c)."""
+    import numpy as np
+    c = ctx or default_context()
+    d = np.ascontiguousarray(np.asarray(desc, dtype=np.int64).reshape(-1, 8))
+    n = int(d.shape[0])
+    dev = leaves.device
+    for t in (namespaces, leaves, nodes, roots):
+        if t.dtype != torch.uint8 or t.device != dev or not t.is_contiguous():
+            raise ValueError("namespaces, leaves, nodes and roots must be contiguous uint8 tensors on one device")
+    n_leaves = leaves.numel() // leaf_len if leaf_len else int(d[:, 2].clip(min=0).sum())
+    n_proven = int(d[:, 2].clip(min=0, max=max(n_leaves, 0)).sum())
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.stream(s):
+        status = torch.empty((n,), dtype=torch.int32, device=dev)
+        if workspace is None:
+            workspace = torch.empty((c._L.dagpu_nmt_verify_workspace_size(n, n_proven),), dtype=torch.uint8,
+                                    device=dev)
+    if workspace.numel() < c._L.dagpu_nmt_verify_workspace_size(n, n_proven):
+        raise ValueError("workspace smaller than dagpu_nmt_verify_workspace_size")
+    rc = c._L.dagpu_nmt_verify_batch_device(
+        c.handle, n, _abi.addr(d), _abi.addr(namespaces), namespaces.numel() // 29, _abi.addr(leaves), n_leaves,
+        leaf_len, _abi.addr(nodes), nodes.numel() // ROOT, _abi.addr(roots), roots.numel() // ROOT,
+        _abi.addr(status), _abi.addr(workspace), _stream_handle(s))
+    if rc != 0:
+        raise DAError(rc, c.last_error())
+    return status
+
+
 class DeviceSquares:
     """n squares of width k resident on one GPU.
 

@@ -8,6 +8,8 @@
   verification: ShareProof.Validate / VerifyProof, RowProof.Validate (celestia-core
   types/share_proof.go, row_proof.go), merkle Proof.Verify, nmt Proof.VerifyInclusion
   -> dagpu_merkle_verify / dagpu_nmt_verify_inclusion (host code of the library)
+  many proofs at once (validate_batch, verify_inclusion_batch, merkle_verify_batch)
+  -> dagpu_merkle_verify_batch / dagpu_nmt_verify_batch (hashed on the GPU)
 
 The square is extended and hashed on the GPU, every row-tree node stays in HBM
 (dagpu_row_nodes_device) and the RFC-6962 tree over rowRoots||colRoots is
@@ -161,6 +163,234 @@ class ShareProof:
 
 def _bytes(b: bytes) -> np.ndarray:
     return np.frombuffer(b, np.uint8) if len(b) else np.zeros(1, np.uint8)
+
+
+# ---------------------------------------------------------------------------
+# Many proofs in one call (dagpu_nmt_verify_batch / dagpu_merkle_verify_batch):
+# the hashing of ShareProof.Validate / RowProof.Validate for a whole list of
+# proofs runs on the GPU; the reference consumer is VerifyShares
+# (x/blobstream/client/verify.go:216-227).
+# ---------------------------------------------------------------------------
+
+@dataclass
+class PackedNMT:
+    """Flat arrays of dagpu_nmt_verify_batch for proofs of one leaf length.
+    desc row = (start, end, n_leaves, leaf_off, n_nodes, node_off, ns_index,
+    root_index); equal namespaces and equal roots are stored once."""
+    desc: np.ndarray
+    namespaces: bytes
+    n_ns: int
+    leaves: bytes
+    n_leaves: int
+    leaf_len: int
+    nodes: bytes
+    n_nodes: int
+    roots: bytes
+    n_roots: int
+
+
+@dataclass
+class PackedMerkle:
+    """Flat arrays of dagpu_merkle_verify_batch for leaves of one length.
+    desc row = (index, total, n_aunts, aunt_off, leaf_index, root_index)."""
+    desc: np.ndarray
+    leaves: bytes
+    n_leaves: int
+    leaf_len: int
+    leaf_hashes: bytes
+    aunts: bytes
+    n_aunts: int
+    roots: bytes
+    n_roots: int
+
+
+def _intern(table: dict, key: bytes) -> int:
+    return table.setdefault(key, len(table))
+
+
+def _i64(v: int) -> int:
+    # a descriptor word is an int64: anything wider cannot be a valid proof
+    # field and is clamped to a value the verifier rejects the same way
+    return max(-(1 << 63), min((1 << 63) - 1, int(v)))
+
+
+def pack_nmt_proofs(items: Sequence[Tuple[NMTProof, bytes, Sequence[bytes], bytes]], leaf_len: int) -> PackedNMT:
+    """items: (proof, namespace, leaves, root) with 29-B namespaces, 90-B roots
+    and nodes and leaves of leaf_len bytes (verify_inclusion_batch sorts out the
+    others beforehand)."""
+    nss, roots = {}, {}
+    desc = np.zeros((len(items), 8), np.int64)
+    leaves, nodes = [], []
+    n_leaves = n_nodes = 0
+    for i, (p, ns, lv, root) in enumerate(items):
+        desc[i] = (_i64(p.start), _i64(p.end), len(lv), n_leaves, len(p.nodes), n_nodes,
+                   _intern(nss, bytes(ns)), _intern(roots, bytes(root)))
+        leaves.extend(bytes(x) for x in lv)
+        nodes.extend(bytes(x) for x in p.nodes)
+        n_leaves += len(lv)
+        n_nodes += len(p.nodes)
+    return PackedNMT(desc, b"".join(nss), len(nss), b"".join(leaves), n_leaves, leaf_len,
+                     b"".join(nodes), n_nodes, b"".join(roots), len(roots))
+
+
+def pack_merkle_proofs(items: Sequence[Tuple[MerkleProof, bytes, bytes]], leaf_len: int) -> PackedMerkle:
+    """items: (proof, root, leaf) with 32-B roots, aunts and leaf hashes and
+    leaves of leaf_len bytes."""
+    roots = {}
+    desc = np.zeros((len(items), 6), np.int64)
+    aunts = []
+    n_aunts = 0
+    for i, (p, root, leaf) in enumerate(items):
+        desc[i] = (_i64(p.index), _i64(p.total), len(p.aunts), n_aunts, i, _intern(roots, bytes(root)))
+        aunts.extend(bytes(a) for a in p.aunts)
+        n_aunts += len(p.aunts)
+    return PackedMerkle(desc, b"".join(bytes(leaf) for _, _, leaf in items), len(items), leaf_len,
+                        b"".join(bytes(p.leaf_hash) for p, _, _ in items), b"".join(aunts), n_aunts,
+                        b"".join(roots), len(roots))
+
+
+def _run_nmt(pk: PackedNMT, c: Context) -> np.ndarray:
+    status = np.full(len(pk.desc), _abi.ERR_ARG, np.int32)
+    desc = np.ascontiguousarray(pk.desc)
+    ns, lv, nd, rt = _bytes(pk.namespaces), _bytes(pk.leaves), _bytes(pk.nodes), _bytes(pk.roots)
+    c.check(c._L.dagpu_nmt_verify_batch(c.handle, len(desc), _abi.addr(desc), _abi.addr(ns), pk.n_ns,
+                                        _abi.addr(lv), pk.n_leaves, pk.leaf_len, _abi.addr(nd), pk.n_nodes,
+                                        _abi.addr(rt), pk.n_roots, _abi.addr(status)))
+    return status
+
+
+def _run_merkle(pk: PackedMerkle, c: Context) -> np.ndarray:
+    status = np.full(len(pk.desc), _abi.ERR_ARG, np.int32)
+    desc = np.ascontiguousarray(pk.desc)
+    lv, lh, au, rt = _bytes(pk.leaves), _bytes(pk.leaf_hashes), _bytes(pk.aunts), _bytes(pk.roots)
+    c.check(c._L.dagpu_merkle_verify_batch(c.handle, len(desc), _abi.addr(desc), _abi.addr(lv), pk.n_leaves,
+                                           pk.leaf_len, _abi.addr(lh), _abi.addr(au), pk.n_aunts,
+                                           _abi.addr(rt), pk.n_roots, _abi.addr(status)))
+    return status
+
+
+def _by_length(entries):
+    """entries: (position, length, item) -> {length: [(position, item)]}."""
+    groups = {}
+    for pos, ln, it in entries:
+        groups.setdefault(ln, []).append((pos, it))
+    return groups
+
+
+def verify_inclusion_batch(items: Sequence[Tuple[NMTProof, bytes, Sequence[bytes], bytes]],
+                           ctx: Optional[Context] = None) -> List[bool]:
+    """NMTProof.verify_inclusion for every (proof, namespace, leaves, root) of
+    `items`, hashed on the GPU: one dagpu_nmt_verify_batch call per distinct
+    leaf length (one call when all leaves are shares)."""
+    out = [False] * len(items)
+    entries = []
+    for i, (p, ns, lv, root) in enumerate(items):
+        if len(ns) != 29 or len(root) != 90 or any(len(n) != 90 for n in p.nodes):
+            continue
+        ln = len(lv[0]) if lv else 0
+        if any(len(x) != ln for x in lv):
+            continue
+        entries.append((i, ln, (p, ns, lv, root)))
+    if not entries:
+        return out
+    c = ctx or default_context()
+    for ln, group in _by_length(entries).items():
+        st = _run_nmt(pack_nmt_proofs([it for _, it in group], ln), c)
+        for (pos, _), s in zip(group, st):
+            out[pos] = int(s) == _abi.OK
+    return out
+
+
+def merkle_verify_batch(items: Sequence[Tuple[MerkleProof, bytes, bytes]],
+                        ctx: Optional[Context] = None) -> List[bool]:
+    """MerkleProof.verify for every (proof, root, leaf): True where verify
+    returns, False where it raises.  Leaf hashes, the LeafHash compare and the
+    aunts run on the GPU: one dagpu_merkle_verify_batch call per distinct leaf
+    length (one call for row roots)."""
+    out = [False] * len(items)
+    entries = []
+    for i, (p, root, leaf) in enumerate(items):
+        if root is None or len(root) != 32 or p.total < 0 or p.index < 0 or len(p.aunts) > MAX_AUNTS:
+            continue
+        if len(p.leaf_hash) != 32 or any(len(a) != 32 for a in p.aunts):
+            continue
+        entries.append((i, len(leaf), (p, root, leaf)))
+    if not entries:
+        return out
+    c = ctx or default_context()
+    for ln, group in _by_length(entries).items():
+        st = _run_merkle(pack_merkle_proofs([it for _, it in group], ln), c)
+        for (pos, _), s in zip(group, st):
+            out[pos] = int(s) == _abi.OK
+    return out
+
+
+def _shape_error(p: "ShareProof") -> Optional[DAError]:
+    """The checks ShareProof.validate and RowProof.validate make before any
+    hash, in their order."""
+    n = sum(sp.end - sp.start for sp in p.share_proofs)
+    if len(p.share_proofs) != len(p.row_proof.row_roots):
+        return DAError(_abi.ERR_PROOF, f"the number of share proofs {len(p.share_proofs)} must equal the "
+                                       f"number of row roots {len(p.row_proof.row_roots)}")
+    if len(p.data) != n:
+        return DAError(_abi.ERR_PROOF, f"the number of shares {len(p.data)} must equal the number of "
+                                       f"shares in share proofs {n}")
+    for sp in p.share_proofs:
+        if sp.start < 0:
+            return DAError(_abi.ERR_PROOF, f"proof index cannot be negative: {sp.start}")
+        if sp.end - sp.start <= 0:
+            return DAError(_abi.ERR_PROOF, f"proof total must be positive: {sp.end - sp.start}")
+    rp = p.row_proof
+    if rp.end_row - rp.start_row + 1 != len(rp.row_roots):
+        return DAError(_abi.ERR_PROOF, "the number of rows is different than the number of row roots")
+    if len(rp.proofs) != len(rp.row_roots):
+        return DAError(_abi.ERR_PROOF, "the number of proofs is different than the number of row roots")
+    return None
+
+
+def validate_batch(proofs: Sequence["ShareProof"], roots, ctx: Optional[Context] = None
+                   ) -> List[Optional[DAError]]:
+    """ShareProof.validate for every proof of a list: entry i is None where
+    proofs[i].validate(root_i) returns and the DAError it raises otherwise.
+    `roots` is one data root or one per proof.  The shape checks run here in the
+    reference's order; every row proof of the list is then hashed by one
+    merkle_verify_batch and every share proof by one verify_inclusion_batch."""
+    if isinstance(roots, (bytes, bytearray)) or roots is None:
+        roots = [roots] * len(proofs)
+    if len(roots) != len(proofs):
+        raise DAError(_abi.ERR_ARG, f"{len(roots)} data roots for {len(proofs)} proofs")
+    out: List[Optional[DAError]] = [_shape_error(p) for p in proofs]
+    m_items, m_owner, n_items, n_owner = [], [], [], []
+    for i, (p, root) in enumerate(zip(proofs, roots)):
+        if out[i] is not None:
+            continue
+        for mp, rr in zip(p.row_proof.proofs, p.row_proof.row_roots):
+            m_items.append((mp, root, rr))
+            m_owner.append(i)
+        if p.namespace_version > 255:
+            continue
+        ns = bytes([p.namespace_version]) + p.namespace_id
+        cursor = 0
+        for j, sp in enumerate(p.share_proofs):
+            used = sp.end - sp.start
+            n_items.append((sp, ns, p.data[cursor:cursor + used], p.row_proof.row_roots[j]))
+            n_owner.append(i)
+            cursor += used
+    row_bad, share_bad = set(), set()
+    for i, ok in zip(m_owner, merkle_verify_batch(m_items, ctx) if m_items else []):
+        if not ok:
+            row_bad.add(i)
+    for i, ok in zip(n_owner, verify_inclusion_batch(n_items, ctx) if n_items else []):
+        if not ok:
+            share_bad.add(i)
+    for i, p in enumerate(proofs):
+        if out[i] is not None:
+            continue
+        if i in row_bad:
+            out[i] = DAError(_abi.ERR_PROOF, "row proof failed to verify")
+        elif p.namespace_version > 255 or i in share_bad:
+            out[i] = DAError(_abi.ERR_PROOF, "share proof failed to verify")
+    return out
 
 
 def merkle_levels(items: Sequence[bytes], ctx: Optional[Context] = None) -> List[List[bytes]]:

@@ -9,6 +9,11 @@
 //   dagpu_blob_commitments inclusion.CreateCommitment over already-split blob
 //                          shares (pkg/inclusion/commitment.go:19-75,
 //                          blob_share_commitment_rules.go:76-101)
+//   dagpu_nmt_verify_batch / dagpu_nmt_verify_batch_device / dagpu_merkle_verify_batch
+//                          nmt Proof.VerifyInclusion and crypto/merkle Proof.Verify
+//                          for many proofs (celestia-core ShareProof.Validate /
+//                          RowProof.Validate; consumer x/blobstream/client/verify.go:216-227),
+//                          hashed on the device (proof_verify.hip)
 // Each call uploads the pushes once, hashes every leaf and level of every
 // tree in a handful of launches (nmt_forest.hip) and returns the roots.
 #include <hip/hip_runtime.h>
@@ -24,6 +29,7 @@
 #include "forest.hpp"
 #include "kernels.hpp"
 #include "host_sha256.hpp"
+#include "proof_verify.hpp"
 #include "runtime.hpp"
 
 namespace {
@@ -126,6 +132,92 @@ std::vector<long> mmr_sizes(uint64_t total, uint64_t max_tree) {
   }
   return out;
 }
+
+// ---- batched proof verification (proof_verify.hip) ----
+
+size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// off >= 0, cnt >= 0 and [off, off + cnt) inside [0, total)
+bool pv_span_ok(int64_t off, int64_t cnt, size_t total) {
+  return off >= 0 && cnt >= 0 && (uint64_t)off <= (uint64_t)total && (uint64_t)cnt <= (uint64_t)total - (uint64_t)off;
+}
+
+// A range nmt Proof.VerifyInclusion rejects before it hashes (trees.cpp
+// dagpu_nmt_verify_inclusion).  end > 2^62: the host verifier's doubling of
+// `est` cannot reach it; no tree is that wide.
+bool pv_range_rejected(const int64_t* d) {
+  const int64_t start = d[0], end = d[1], nl = d[2];
+  return start < 0 || start >= end || end > ((int64_t)1 << kPvMaxHeight) || nl != end - start;
+}
+
+// Host image of what the nmt kernels read besides the bulk data.
+struct PvNmtPlan {
+  std::vector<int64_t> meta;  // desc (8 n) | rec_off (n + 1) | cs_off (n + 1)
+  long n_records = 0, n_stack = 0;
+};
+
+// Every descriptor against the totals; nothing is launched when one fails.
+int pv_check_nmt(dagpu_ctx* ctx, size_t n, const int64_t* desc, size_t n_ns, size_t n_leaves, size_t n_nodes,
+                 size_t n_roots, PvNmtPlan* plan) {
+  plan->meta.resize(n * kPvDescNmt + 2 * (n + 1));
+  int64_t* rec_off = plan->meta.data() + n * kPvDescNmt;
+  int64_t* cs_off = rec_off + (n + 1);
+  long recs = 0, stack = 0;
+  for (size_t i = 0; i < n; i++) {
+    const int64_t* d = desc + i * kPvDescNmt;
+    if (!pv_span_ok(d[3], d[2], n_leaves) || !pv_span_ok(d[5], d[4], n_nodes) || d[4] > INT32_MAX ||
+        d[6] < 0 || (uint64_t)d[6] >= n_ns || d[7] < 0 || (uint64_t)d[7] >= n_roots)
+      return set_err(ctx, DAGPU_ERR_ARG, "proof descriptor " + std::to_string(i) + " points outside the buffers");
+    memcpy(plan->meta.data() + i * kPvDescNmt, d, kPvDescNmt * sizeof(int64_t));
+    rec_off[i] = recs;
+    cs_off[i] = stack;
+    if (!pv_range_rejected(d)) {
+      recs += (long)d[2];
+      stack += pv_stack_depth(d[2]);
+    }
+  }
+  rec_off[n] = recs;
+  cs_off[n] = stack;
+  plan->n_records = recs;
+  plan->n_stack = stack;
+  return DAGPU_OK;
+}
+
+size_t pv_nmt_meta_bytes(size_t n) { return align256((n * kPvDescNmt + 2 * (n + 1)) * sizeof(int64_t)); }
+
+// Upload the plan and enqueue the leaf and fold passes.  Returns once the
+// upload is complete (the plan and the caller's descriptors may go).
+int pv_nmt_enqueue(dagpu_ctx* ctx, size_t n, const PvNmtPlan& plan, const uint8_t* d_ns, const uint8_t* d_leaves,
+                   size_t leaf_len, const uint8_t* d_nodes, const uint8_t* d_roots, int32_t* d_status,
+                   uint8_t* d_ws, hipStream_t s) {
+  HIP_TRY(ctx, hipMemcpyAsync(d_ws, plan.meta.data(), plan.meta.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+  PvNmtArgs a{};
+  a.n = (long)n;
+  a.desc = (const int64_t*)d_ws;
+  a.rec_off = a.desc + n * kPvDescNmt;
+  a.cs_off = a.rec_off + (n + 1);
+  a.ns = d_ns;
+  a.leaves = d_leaves;
+  a.leaf_len = (long)leaf_len;
+  a.fast512 = leaf_len == (size_t)kShareSize && (((uintptr_t)d_leaves) & 15) == 0;
+  a.nodes = d_nodes;
+  a.roots = d_roots;
+  a.recs = d_ws + pv_nmt_meta_bytes(n);
+  a.cstack = a.recs + (size_t)plan.n_records * kRecNmt;
+  a.status = d_status;
+  HIP_TRY(ctx, launch_pv_nmt_leaves(a, plan.n_records, s));
+  HIP_TRY(ctx, launch_pv_nmt_fold(a, s));
+  return DAGPU_OK;
+}
+
+// One device allocation for a host-form call, freed on every path.
+struct PvScratch {
+  void* p = nullptr;
+  ~PvScratch() {
+    if (p) (void)hipFree(p);
+  }
+};
 
 }  // namespace
 
@@ -401,6 +493,114 @@ int dagpu_merkle_verify(const uint8_t* root32, const uint8_t* leaf, size_t leaf_
   uint8_t root[32];
   if (!up(index, total, naunts, root)) return DAGPU_ERR_PROOF;
   return memcmp(root, root32, 32) == 0 ? DAGPU_OK : DAGPU_ERR_PROOF;
+}
+
+size_t dagpu_nmt_verify_workspace_size(size_t n, size_t n_leaves) {
+  // descriptors and offsets, one 96-B record per proven leaf, and the fold's
+  // record stack: pv_stack_depth(nl) <= nl + 3 per proof
+  return pv_nmt_meta_bytes(n) + (size_t)kRecNmt * (2 * n_leaves + 3 * n) + 256;
+}
+
+int dagpu_nmt_verify_batch_device(dagpu_ctx* ctx, size_t n, const int64_t* desc, const uint8_t* d_namespaces,
+                                  size_t n_ns, const uint8_t* d_leaves, size_t n_leaves, size_t leaf_len,
+                                  const uint8_t* d_nodes, size_t n_nodes, const uint8_t* d_roots, size_t n_roots,
+                                  int32_t* d_status, void* d_workspace, void* stream) {
+  if (!ctx) return DAGPU_ERR_ARG;
+  if (n == 0) return DAGPU_OK;
+  if (!desc || !d_status || !d_workspace || (((uintptr_t)d_workspace) & 15) != 0 || (n_ns && !d_namespaces) ||
+      (n_leaves && leaf_len && !d_leaves) || (n_nodes && !d_nodes) || (n_roots && !d_roots))
+    return set_err(ctx, DAGPU_ERR_ARG, "dagpu_nmt_verify_batch_device: null or misaligned buffer");
+  PvNmtPlan plan;
+  int rc = pv_check_nmt(ctx, n, desc, n_ns, n_leaves, n_nodes, n_roots, &plan);
+  if (rc) return rc;
+  return pv_nmt_enqueue(ctx, n, plan, d_namespaces, d_leaves, leaf_len, d_nodes, d_roots, d_status,
+                        (uint8_t*)d_workspace, (hipStream_t)stream);
+}
+
+int dagpu_nmt_verify_batch(dagpu_ctx* ctx, size_t n, const int64_t* desc, const uint8_t* namespaces, size_t n_ns,
+                           const uint8_t* leaves, size_t n_leaves, size_t leaf_len, const uint8_t* nodes,
+                           size_t n_nodes, const uint8_t* roots, size_t n_roots, int32_t* status) {
+  if (!ctx) return DAGPU_ERR_ARG;
+  if (n == 0) return DAGPU_OK;
+  if (!desc || !status || (n_ns && !namespaces) || (n_leaves && leaf_len && !leaves) || (n_nodes && !nodes) ||
+      (n_roots && !roots))
+    return set_err(ctx, DAGPU_ERR_ARG, "dagpu_nmt_verify_batch: null buffer");
+  PvNmtPlan plan;
+  int rc = pv_check_nmt(ctx, n, desc, n_ns, n_leaves, n_nodes, n_roots, &plan);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  (void)hipSetDevice(ctx->device);
+  hipStream_t s = ctx->stream;
+  const size_t b_ns = n_ns * kNsSize, b_lv = n_leaves * leaf_len, b_nd = n_nodes * kNodeSize,
+               b_rt = n_roots * kNodeSize;
+  const size_t o_ns = 0, o_lv = o_ns + align256(b_ns), o_nd = o_lv + align256(b_lv), o_rt = o_nd + align256(b_nd),
+               o_st = o_rt + align256(b_rt), o_ws = o_st + align256(4 * n);
+  const size_t ws = pv_nmt_meta_bytes(n) + (size_t)kRecNmt * (size_t)(plan.n_records + plan.n_stack) + 256;
+  PvScratch m;
+  HIP_TRY(ctx, hipMalloc(&m.p, o_ws + ws));
+  uint8_t* d = (uint8_t*)m.p;
+  if (b_ns) HIP_TRY(ctx, hipMemcpyAsync(d + o_ns, namespaces, b_ns, hipMemcpyHostToDevice, s));
+  if (b_lv) HIP_TRY(ctx, hipMemcpyAsync(d + o_lv, leaves, b_lv, hipMemcpyHostToDevice, s));
+  if (b_nd) HIP_TRY(ctx, hipMemcpyAsync(d + o_nd, nodes, b_nd, hipMemcpyHostToDevice, s));
+  if (b_rt) HIP_TRY(ctx, hipMemcpyAsync(d + o_rt, roots, b_rt, hipMemcpyHostToDevice, s));
+  rc = pv_nmt_enqueue(ctx, n, plan, d + o_ns, d + o_lv, leaf_len, d + o_nd, d + o_rt, (int32_t*)(d + o_st),
+                      d + o_ws, s);
+  if (rc) {
+    (void)hipStreamSynchronize(s);
+    return rc;
+  }
+  std::vector<int32_t> st(n);
+  HIP_TRY(ctx, hipMemcpyAsync(st.data(), d + o_st, 4 * n, hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+  memcpy(status, st.data(), 4 * n);
+  return DAGPU_OK;
+}
+
+int dagpu_merkle_verify_batch(dagpu_ctx* ctx, size_t n, const int64_t* desc, const uint8_t* leaves, size_t n_leaves,
+                              size_t leaf_len, const uint8_t* leaf_hashes, const uint8_t* aunts, size_t n_aunts,
+                              const uint8_t* roots32, size_t n_roots, int32_t* status) {
+  if (!ctx) return DAGPU_ERR_ARG;
+  if (n == 0) return DAGPU_OK;
+  if (!desc || !status || (n_leaves && leaf_len && !leaves) || (n_aunts && !aunts) || (n_roots && !roots32))
+    return set_err(ctx, DAGPU_ERR_ARG, "dagpu_merkle_verify_batch: null buffer");
+  for (size_t i = 0; i < n; i++) {
+    const int64_t* d = desc + i * kPvDescMerkle;
+    if (!pv_span_ok(d[3], d[2], n_aunts) || d[4] < 0 || (uint64_t)d[4] >= n_leaves || d[5] < 0 ||
+        (uint64_t)d[5] >= n_roots)
+      return set_err(ctx, DAGPU_ERR_ARG, "proof descriptor " + std::to_string(i) + " points outside the buffers");
+  }
+  std::lock_guard<std::mutex> g(ctx->mu);
+  (void)hipSetDevice(ctx->device);
+  hipStream_t s = ctx->stream;
+  const size_t b_ds = n * kPvDescMerkle * sizeof(int64_t), b_lv = n_leaves * leaf_len, b_lh = leaf_hashes ? 32 * n : 0,
+               b_au = 32 * n_aunts, b_rt = 32 * n_roots;
+  const size_t o_ds = 0, o_lv = o_ds + align256(b_ds), o_lh = o_lv + align256(b_lv), o_au = o_lh + align256(b_lh),
+               o_rt = o_au + align256(b_au), o_st = o_rt + align256(b_rt);
+  PvScratch m;
+  HIP_TRY(ctx, hipMalloc(&m.p, o_st + align256(4 * n)));
+  uint8_t* d = (uint8_t*)m.p;
+  HIP_TRY(ctx, hipMemcpyAsync(d + o_ds, desc, b_ds, hipMemcpyHostToDevice, s));
+  if (b_lv) HIP_TRY(ctx, hipMemcpyAsync(d + o_lv, leaves, b_lv, hipMemcpyHostToDevice, s));
+  if (b_lh) HIP_TRY(ctx, hipMemcpyAsync(d + o_lh, leaf_hashes, b_lh, hipMemcpyHostToDevice, s));
+  if (b_au) HIP_TRY(ctx, hipMemcpyAsync(d + o_au, aunts, b_au, hipMemcpyHostToDevice, s));
+  if (b_rt) HIP_TRY(ctx, hipMemcpyAsync(d + o_rt, roots32, b_rt, hipMemcpyHostToDevice, s));
+  PvMerkleArgs a{};
+  a.n = (long)n;
+  a.desc = (const int64_t*)(d + o_ds);
+  a.leaves = d + o_lv;
+  a.leaf_len = (long)leaf_len;
+  a.leaf_hashes = leaf_hashes ? d + o_lh : nullptr;
+  a.aunts = d + o_au;
+  a.roots = d + o_rt;
+  a.status = (int32_t*)(d + o_st);
+  hipError_t e = launch_pv_merkle(a, s);
+  std::vector<int32_t> st(n);
+  if (e == hipSuccess) e = hipMemcpyAsync(st.data(), d + o_st, 4 * n, hipMemcpyDeviceToHost, s);
+  const hipError_t e2 = hipStreamSynchronize(s);  // the uploads read caller memory: always wait
+  HIP_TRY(ctx, e);
+  HIP_TRY(ctx, e2);
+  memcpy(status, st.data(), 4 * n);
+  return DAGPU_OK;
 }
 
 int dagpu_subtree_width(uint64_t share_count, uint32_t subtree_root_threshold) {

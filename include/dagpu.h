@@ -339,6 +339,63 @@ int dagpu_nmt_verify_inclusion(const uint8_t* ns29, const uint8_t* leaves, size_
 int dagpu_merkle_verify(const uint8_t* root32, const uint8_t* leaf, size_t leaf_len, int64_t index,
                         int64_t total, const uint8_t* aunts, size_t naunts);
 
+/* ---- Many proofs verified in one call, hashed on the GPU ----------------
+ * nmt Proof.VerifyInclusion and crypto/merkle Proof.Verify for a batch: what
+ * celestia-core ShareProof.Validate / RowProof.Validate do row by row, and what
+ * the reference's x/blobstream/client/verify.go:216-227 (VerifyShares) asks of
+ * them, for every proof of a list at once.  The specification is the two host
+ * verifiers above: status[i] is exactly what dagpu_nmt_verify_inclusion /
+ * dagpu_merkle_verify returns for proof i (DAGPU_OK or DAGPU_ERR_PROOF; proof
+ * byte order as there, "parity unpinned").
+ *
+ * A proof is one fixed record of int64 in HOST memory (both call forms);
+ * offsets count leaves / nodes / aunts, and ranges of different proofs may
+ * overlap in every buffer:
+ *   nmt     desc[8i..]  = { start, end, n_leaves, leaf_off, n_nodes, node_off,
+ *                           ns_index, root_index }
+ *           leaves leaf_off .. leaf_off + n_leaves (leaf_len bytes each, WITHOUT
+ *           the namespace), nodes node_off .. (90 B each), namespace ns_index
+ *           of `namespaces` (29 B each), root root_index of `roots` (90 B each).
+ *   merkle  desc[6i..]  = { index, total, n_aunts, aunt_off, leaf_index,
+ *                           root_index }
+ *           leaf leaf_index of `leaves` (leaf_len bytes each), aunts aunt_off ..
+ *           (32 B each, leaf to root), root root_index of `roots32`.
+ * Every descriptor is checked before anything is launched: an offset or index
+ * outside the stated totals (or negative, or n_nodes > INT32_MAX) fails the
+ * whole call with DAGPU_ERR_ARG and leaves `status` untouched.  A range the
+ * host verifier rejects (start < 0, start >= end, n_leaves != end - start; also
+ * end > 2^62, where the host verifier does not terminate) gives that proof
+ * DAGPU_ERR_PROOF and does not fail the call.  The call returns DAGPU_OK when
+ * it ran, whatever the per-proof results.
+ *
+ * dagpu_nmt_verify_batch: every buffer in host memory.
+ * dagpu_nmt_verify_batch_device: bulk data and `d_status` (n int32) in device
+ * memory; d_workspace (16-B aligned) of dagpu_nmt_verify_workspace_size(n, m)
+ * bytes, m >= the sum of desc[i].n_leaves.  The call returns when the
+ * descriptors are uploaded (it waits for `stream` up to that copy, and `desc`
+ * may be freed); the kernels are enqueued only.  With leaf_len == 512,
+ * d_leaves may be an extended square itself (cell (r, c) = leaf r * 2k + c):
+ * samples of a resident square are verified without a copy.
+ * dagpu_merkle_verify_batch: host memory; leaf_hashes (n x 32 B, optional) are
+ * the proofs' own LeafHash fields, a mismatch with leafHash(leaf) gives
+ * DAGPU_ERR_PROOF as in Proof.Verify. */
+#define DAGPU_NMT_DESC_WORDS 8
+#define DAGPU_MERKLE_DESC_WORDS 6
+int dagpu_nmt_verify_batch(dagpu_ctx* ctx, size_t n, const int64_t* desc, const uint8_t* namespaces,
+                           size_t n_ns, const uint8_t* leaves, size_t n_leaves, size_t leaf_len,
+                           const uint8_t* nodes, size_t n_nodes, const uint8_t* roots, size_t n_roots,
+                           int32_t* status);
+size_t dagpu_nmt_verify_workspace_size(size_t n, size_t n_leaves);
+int dagpu_nmt_verify_batch_device(dagpu_ctx* ctx, size_t n, const int64_t* desc,
+                                  const uint8_t* d_namespaces, size_t n_ns, const uint8_t* d_leaves,
+                                  size_t n_leaves, size_t leaf_len, const uint8_t* d_nodes, size_t n_nodes,
+                                  const uint8_t* d_roots, size_t n_roots, int32_t* d_status,
+                                  void* d_workspace, void* stream);
+int dagpu_merkle_verify_batch(dagpu_ctx* ctx, size_t n, const int64_t* desc, const uint8_t* leaves,
+                              size_t n_leaves, size_t leaf_len, const uint8_t* leaf_hashes,
+                              const uint8_t* aunts, size_t n_aunts, const uint8_t* roots32, size_t n_roots,
+                              int32_t* status);
+
 /* inclusion.SubTreeWidth (pkg/inclusion/blob_share_commitment_rules.go:85-101). */
 int dagpu_subtree_width(uint64_t share_count, uint32_t subtree_root_threshold);
 
