@@ -25,6 +25,7 @@
 #include "../../include/dagpu.h"
 #include "host_sha256.hpp"
 #include "kernels.hpp"
+#include "pipe_carve.hpp"
 #include "runtime.hpp"
 
 using namespace dagpu;
@@ -36,7 +37,8 @@ size_t ods_bytes(uint64_t k) { return 1ull * k * k * kSS; }
 
 // RS extension of n squares (uniform k), device pointers.
 // ev_rows (optional) is recorded between the row and the column pass: rows
-// 0..k-1 of every EDS ([Q0|Q1]) are final from that point on.
+// 0..k-1 of every EDS ([Q0|Q1]) are final from that point on (the host path
+// starts the EDS download there, the sliced device batch the top-half leaves).
 int enqueue_rs(dagpu_ctx* ctx, uint32_t k, size_t n, const uint8_t* d_ods, uint8_t* d_eds,
                hipStream_t s, hipEvent_t ev_rows = nullptr) {
   const long w = 2L * k;
@@ -96,7 +98,8 @@ int enqueue_rs(dagpu_ctx* ctx, uint32_t k, size_t n, const uint8_t* d_ods, uint8
   return DAGPU_OK;
 }
 
-// d_dah = NULL: roots only (Repair's verification needs no DAH)
+// d_dah = NULL: roots only (Repair's verification needs no DAH).  The leaf
+// launch clears the status words (no memset in front of it).
 int enqueue_roots(dagpu_ctx* ctx, uint32_t k, size_t n, const uint8_t* d_eds, uint8_t* d_rr,
                   uint8_t* d_cr, uint8_t* d_dah, int32_t* d_status, void* d_ws, hipStream_t s) {
   SquareArgs sa{};
@@ -111,10 +114,9 @@ int enqueue_roots(dagpu_ctx* ctx, uint32_t k, size_t n, const uint8_t* d_eds, ui
   sa.status = d_status;
   sa.k = (int)k;
   sa.nsq = (long)n;
-  HIP_TRY(ctx, hipMemsetAsync(d_status, 0, n * sizeof(int32_t), s));
   {
     ProfScope p(ctx, 2, s);
-    HIP_TRY(ctx, launch_nmt_leaves(sa, s));
+    HIP_TRY(ctx, launch_nmt_leaves(sa, s, 0, -1, true));
   }
   stage_mark(ctx, DAGPU_STAGE_LEAVES, s);
   {
@@ -127,6 +129,110 @@ int enqueue_roots(dagpu_ctx* ctx, uint32_t k, size_t n, const uint8_t* d_eds, ui
     HIP_TRY(ctx, launch_dah(sa, s));
   }
   stage_mark(ctx, DAGPU_STAGE_DAH, s);
+  return DAGPU_OK;
+}
+
+// Events of one pipelined call, back in the pool on every return path.
+struct EventSet {
+  dagpu_ctx* c;
+  std::vector<hipEvent_t> v;
+  explicit EventSet(dagpu_ctx* ctx) : c(ctx) {}
+  ~EventSet() {
+    for (auto e : v) ev_give(c, e);
+  }
+  bool take(size_t n) {
+    for (size_t i = 0; i < n; i++) {
+      hipEvent_t e = ev_take(c);
+      if (!e) return false;
+      v.push_back(e);
+    }
+    return true;
+  }
+};
+
+// dagpu_extend_batch_device with S >= 2 slices.  The RS passes of all slices
+// run in order on a side stream; the caller's stream hashes slice after slice:
+//   top-half leaves (rows 0..k-1: final after the slice's ROW pass, so they
+//   run beside its column pass; they also clear the slice's status words)
+//   |  bottom-half leaves (after the column pass)  |  tree levels 1..cut
+// and then, once over all n squares, tree levels cut+1.. and the DAH: at a
+// slice's size those launches cannot fill the CUs (pipe_carve.hpp has the rule
+// for `cut` and the workspace layout).  Profiling never comes here
+// (pipe_slices), so no launch is bracketed.
+int extend_batch_sliced(dagpu_ctx* ctx, uint32_t k, size_t n, size_t S, const uint8_t* d_ods, uint8_t* d_eds,
+                        uint8_t* d_rr, uint8_t* d_cr, uint8_t* d_dah, int32_t* d_status, void* d_ws,
+                        hipStream_t s) {
+  const size_t w = 2 * (size_t)k;
+  // equal slices (tried and dropped, profiles/pipeline_r02.log, pipe_streams_r03.log, pipe_tails_after.log:
+  // a smaller first slice, a high-priority RS stream, a second NMT stream)
+  std::vector<size_t> cut(S + 1);
+  for (size_t i = 0; i <= S; i++) cut[i] = n * i / S;
+  const size_t m = (n + S - 1) / S;  // the largest slice
+  const int levels = nmt_levels((int)k);
+  // the rule's cut level, or the next one whose batch-wide records still fit in
+  // the caller's workspace (two slices at a low cut do not); none: every slice
+  // runs all its levels in the unsliced layout
+  PipeCarve pc{};
+  for (int cl = pipe_cut_level((int)k, m, nmt_level_fill_blocks()); cl < levels && !pc.defer; cl++)
+    pc = pipe_carve((int)k, n, m, cl, dagpu_workspace_size(k, n));
+  // events: [0, S) a slice's RS done, [S, 2S) its row pass done, [2S] the fork
+  EventSet ev(ctx);
+  if (!ev.take(2 * S + 1)) return set_err(ctx, DAGPU_ERR_DEVICE, "hipEventCreate failed");
+  hipStream_t rs = side_stream(ctx, s, 0);
+  if (!rs) return set_err(ctx, DAGPU_ERR_DEVICE, "hipStreamCreate failed");
+  // fork: the side stream starts after the work already queued on the caller's stream
+  HIP_TRY(ctx, hipEventRecord(ev.v[2 * S], s));
+  HIP_TRY(ctx, hipStreamWaitEvent(rs, ev.v[2 * S], 0));
+  for (size_t i = 0; i < S; i++) {
+    const size_t a = cut[i], b = cut[i + 1];
+    int rc = enqueue_rs(ctx, k, b - a, d_ods ? d_ods + a * ods_bytes(k) : nullptr, d_eds + a * eds_bytes(k), rs,
+                        ev.v[S + i]);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipEventRecord(ev.v[i], rs));
+  }
+  uint8_t* const ws = (uint8_t*)d_ws;
+  SquareArgs all{};  // the whole batch: deferred tree levels and the DAH
+  all.eds = d_eds;
+  all.eds_sq_stride = (long)eds_bytes(k);
+  all.k = (int)k;
+  all.nsq = (long)n;
+  all.digests = ws;  // scratch of the DAH's two-stage variant, free once the trees are built
+  all.ns_table = pc.defer ? ws + pc.ns_all : nullptr;
+  all.row_roots = d_rr;
+  all.col_roots = d_cr;
+  all.dah = d_dah;
+  all.status = d_status;
+  // slices in order on the caller's stream, sharing the slice regions of the
+  // workspace; waiting on the last slice's event joins the RS stream
+  for (size_t i = 0; i < S; i++) {
+    const size_t a = cut[i], b = cut[i + 1];
+    SquareArgs sa = all;
+    sa.eds = d_eds + a * eds_bytes(k);
+    sa.nsq = (long)(b - a);
+    sa.row_roots = d_rr + a * w * kNodeSize;
+    sa.col_roots = d_cr + a * w * kNodeSize;
+    sa.status = d_status + a;
+    if (pc.defer) {
+      sa.digests = ws + pc.digests;
+      sa.rec_a = ws + pc.rec_a;
+      sa.rec_b = ws + pc.rec_b;
+      sa.ns_table = ws + pc.ns_all + a * (size_t)k * k * 32;
+    } else {
+      nmt_workspace_carve(sa, ws);
+    }
+    HIP_TRY(ctx, hipStreamWaitEvent(s, ev.v[S + i], 0));
+    HIP_TRY(ctx, launch_nmt_leaves(sa, s, 0, (int)k, true));
+    HIP_TRY(ctx, hipStreamWaitEvent(s, ev.v[i], 0));
+    HIP_TRY(ctx, launch_nmt_leaves(sa, s, (int)k, (int)k, false));
+    uint8_t* const pp[2] = {sa.rec_b, sa.rec_a};
+    uint8_t* const cut_out = pc.defer ? ws + pc.rec_c + a * nmt_level_rec_bytes((int)k, pc.cut) : nullptr;
+    HIP_TRY(ctx, launch_nmt_tree_levels(sa, 1, pc.defer ? pc.cut : levels, pp, cut_out, s));
+  }
+  if (pc.defer) {
+    uint8_t* const pp[2] = {ws + pc.rec_c, ws + pc.rec_d};
+    HIP_TRY(ctx, launch_nmt_tree_levels(all, pc.cut + 1, levels, pp, nullptr, s));
+  }
+  HIP_TRY(ctx, launch_dah(all, s));
   return DAGPU_OK;
 }
 
@@ -607,12 +713,16 @@ void ev_give(dagpu_ctx* c, hipEvent_t e) {
 // Slices of a device batch for the RS/NMT pipeline: RS of slice i+1.. runs on
 // a side stream while the NMT kernels of slice i run on the caller's stream
 // (bench: 256 squares at k = 128, 4 slices 11.98 -> 11.63 ms; tools/pipe_exp.py).
+// 8 slices from 256 squares on: with the top tree levels and the DAH run once
+// per call (extend_batch_sliced) a slice no longer pays its own tail, and 8
+// beat 4 (profiles/pipe_tails_after.log; measured at 256 squares only, so
+// smaller batches keep 4).
 // DAGPU_PIPE_SLICES overrides (1 = off; read per call, so tests can vary it).
 // Off while profiling, so that every kernel's event bracket times that kernel alone.
 size_t pipe_slices(dagpu_ctx* ctx, uint32_t k, size_t n) {
   const long env = sw_long(SW_PIPE_SLICES);
   if (ctx->prof) return 1;
-  size_t s = env > 0 ? (size_t)env : (k >= 128 && n >= 64 ? 4 : 1);
+  size_t s = env > 0 ? (size_t)env : (k >= 128 && n >= 64 ? (n >= 256 ? 8 : 4) : 1);
   while (s > 1 && n / s < 8) s >>= 1;
   return s < 1 ? 1 : s;
 }
@@ -672,43 +782,7 @@ int dagpu_extend_batch_device(dagpu_ctx* ctx, uint32_t k, size_t n, const uint8_
     if (rc) return rc;
     return enqueue_roots(ctx, k, n, d_eds, d_row_roots, d_col_roots, d_dah, d_status, d_workspace, s);
   }
-  // fork: the side stream starts after the work already queued on the caller's stream
-  std::vector<hipEvent_t> ev(S + 1, nullptr);
-  for (auto& e : ev)
-    if (!(e = ev_take(ctx))) {
-      for (auto x : ev) ev_give(ctx, x);
-      return set_err(ctx, DAGPU_ERR_DEVICE, "hipEventCreate failed");
-    }
-  auto done = [&](int r) {
-    for (auto x : ev) ev_give(ctx, x);
-    return r;
-  };
-  hipStream_t rs = side_stream(ctx, s, 0);
-  if (!rs) return done(set_err(ctx, DAGPU_ERR_DEVICE, "hipStreamCreate failed"));
-  const size_t w = 2 * (size_t)k;
-  if (hipEventRecord(ev[S], s) != hipSuccess || hipStreamWaitEvent(rs, ev[S], 0) != hipSuccess)
-    return done(set_err(ctx, DAGPU_ERR_DEVICE, "pipeline fork failed"));
-  // equal slices (tried and dropped, profiles/pipeline_r02.log, pipe_streams_r03.log:
-  // a smaller first slice, a high-priority RS stream, a second NMT stream)
-  std::vector<size_t> cut(S + 1);
-  for (size_t i = 0; i <= S; i++) cut[i] = n * i / S;
-  for (size_t i = 0; i < S; i++) {
-    const size_t a = cut[i], b = cut[i + 1];
-    rc = enqueue_rs(ctx, k, b - a, d_ods ? d_ods + a * ods_bytes(k) : nullptr, d_eds + a * eds_bytes(k), rs);
-    if (rc) return done(rc);
-    if (hipEventRecord(ev[i], rs) != hipSuccess) return done(set_err(ctx, DAGPU_ERR_DEVICE, "hipEventRecord failed"));
-  }
-  // NMT work of the slices: in order on the caller's stream, sharing the front
-  // of the workspace; waiting on the last slice's event joins the RS stream
-  for (size_t i = 0; i < S; i++) {
-    const size_t a = cut[i], b = cut[i + 1];
-    if (hipStreamWaitEvent(s, ev[i], 0) != hipSuccess)
-      return done(set_err(ctx, DAGPU_ERR_DEVICE, "hipStreamWaitEvent failed"));
-    rc = enqueue_roots(ctx, k, b - a, d_eds + a * eds_bytes(k), d_row_roots + a * w * kNodeSize,
-                       d_col_roots + a * w * kNodeSize, d_dah + a * 32, d_status + a, (uint8_t*)d_workspace, s);
-    if (rc) return done(rc);
-  }
-  return done(DAGPU_OK);
+  return extend_batch_sliced(ctx, k, n, S, d_ods, d_eds, d_row_roots, d_col_roots, d_dah, d_status, d_workspace, s);
 }
 
 int dagpu_roots(dagpu_ctx* ctx, uint32_t k, const uint8_t* eds, uint8_t* row_roots,

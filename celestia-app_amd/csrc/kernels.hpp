@@ -339,11 +339,25 @@ struct SquareArgs {
   long nsq;
 };
 
-hipError_t launch_nmt_leaves(const SquareArgs& a, hipStream_t s);
+// Leaf digests (and Q0 namespaces) of rows [row0, row0 + nrows) of every
+// square (nrows < 0: to the last row).  zero_status (row0 == 0 only): the
+// launch also clears status[0 .. nsq), before the level-1 kernel queued behind
+// it ORs the push-order bit in.
+hipError_t launch_nmt_leaves(const SquareArgs& a, hipStream_t s, int row0 = 0, int nrows = -1,
+                             bool zero_status = false);
 // workspace layout for SquareArgs (digests | ns_table | rec_a | rec_b)
 size_t nmt_workspace_bytes(int k, long nsq);
 void nmt_workspace_carve(SquareArgs& a, void* ws);
 hipError_t launch_nmt_trees(const SquareArgs& a, hipStream_t s);
+// Tree levels first..last: level L reads pp[(L - first) & 1] (level 1: the leaf
+// digests) and writes pp[(L - first + 1) & 1], level `last` writes last_out
+// when given; the top level writes the roots.  Records of square sq of a
+// launch start at sq * nmt_level_rec_bytes (pipe_carve.hpp) in either buffer.
+hipError_t launch_nmt_tree_levels(const SquareArgs& a, int first, int last, uint8_t* const pp[2], uint8_t* last_out,
+                                  hipStream_t s);
+// workgroups of nmt_level_kernel that fill the device: CUs x resident
+// workgroups per CU (0 if the runtime cannot tell)
+long nmt_level_fill_blocks();
 hipError_t launch_dah(const SquareArgs& a, hipStream_t s);
 
 }  // namespace dagpu

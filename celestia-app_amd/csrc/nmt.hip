@@ -32,6 +32,7 @@
 
 #include "kernels.hpp"
 #include "nmt_node.hpp"
+#include "pipe_carve.hpp"
 #include "sha256.hpp"
 
 namespace dagpu {
@@ -49,17 +50,24 @@ namespace dagpu {
 // (DAGPU_LEAF_LDS) fetches the same bytes but runs ~10 % slower (occupancy).
 constexpr int kLeafWave = 256;
 
-__global__ __launch_bounds__(kLeafWave) void nmt_leaf_kernel(SquareArgs a) {
+//
+// A launch covers rows [row0, row0 + nrows) of every square: the pipelined
+// batch hashes rows 0..k-1 ([Q0|Q1], final after the row pass) while the
+// column pass still runs.  With zero_status the lane of cell (0, 0) clears its
+// square's status word, which the level-1 kernel behind it on the stream ORs into.
+__global__ __launch_bounds__(kLeafWave) void nmt_leaf_kernel(SquareArgs a, int row0, int nrows, int zero_status) {
   const int k = a.k;
   const long w = 2L * k;
   const long cells = w * w;
-  const long total = cells * a.nsq;
+  const long span = nrows * w;  // cells of one square in this launch
+  const long total = span * a.nsq;
   const long gid = (long)blockIdx.x * kLeafWave + threadIdx.x;
   if (gid >= total) return;
-  const long sq = gid / cells;
-  const long cell = gid - sq * cells;
+  const long sq = gid / span;
+  const long cell = row0 * w + (gid - sq * span);
   const long r = cell / w, c = cell - (cell / w) * w;
   const bool q0 = (r < k) && (c < k);
+  if (zero_status && cell == 0) a.status[sq] = 0;
   const uint4* src = (const uint4*)(a.eds + sq * a.eds_sq_stride + cell * kShareSize);
   uint32_t st[8], ns[8];
   share_leaf_sha256(src, q0, st, ns);
@@ -68,7 +76,7 @@ __global__ __launch_bounds__(kLeafWave) void nmt_leaf_kernel(SquareArgs a) {
     nsp[0] = make_uint4(ns[0], ns[1], ns[2], ns[3]);
     nsp[1] = make_uint4(ns[4], ns[5], ns[6], ns[7]);
   }
-  uint4* out = (uint4*)(a.digests + gid * kDigest);
+  uint4* out = (uint4*)(a.digests + (sq * cells + cell) * kDigest);
   out[0] = make_uint4(bswap32(st[0]), bswap32(st[1]), bswap32(st[2]), bswap32(st[3]));
   out[1] = make_uint4(bswap32(st[4]), bswap32(st[5]), bswap32(st[6]), bswap32(st[7]));
 }
@@ -425,47 +433,62 @@ __global__ __launch_bounds__(kDahThreads) void dah_top_kernel(SquareArgs a) {
   if (threadIdx.x < 8) ((uint32_t*)(a.dah + sq * 32))[threadIdx.x] = root[threadIdx.x];
 }
 
-hipError_t launch_nmt_leaves(const SquareArgs& a, hipStream_t s) {
+hipError_t launch_nmt_leaves(const SquareArgs& a, hipStream_t s, int row0, int nrows, bool zero_status) {
   const long w = 2L * a.k;
-  const long total = w * w * a.nsq;
+  if (nrows < 0) nrows = (int)w - row0;
+  if (row0 < 0 || nrows <= 0 || row0 + nrows > w || (zero_status && (row0 != 0 || !a.status)))
+    return hipErrorInvalidValue;
+  const long total = nrows * w * a.nsq;
   const long blocks = (total + kLeafWave - 1) / kLeafWave;
-  hipLaunchKernelGGL(nmt_leaf_kernel, dim3((unsigned)blocks), dim3(kLeafWave), 0, s, a);
+  hipLaunchKernelGGL(nmt_leaf_kernel, dim3((unsigned)blocks), dim3(kLeafWave), 0, s, a, row0, nrows,
+                     (int)zero_status);
   return hipGetLastError();
 }
 
-hipError_t launch_nmt_trees(const SquareArgs& a, hipStream_t s) {
+hipError_t launch_nmt_tree_levels(const SquareArgs& a, int first, int last, uint8_t* const pp[2], uint8_t* last_out,
+                                  hipStream_t s) {
   const int w = 2 * a.k;
-  int levels = 0;
-  while ((1 << levels) < w) levels++;
-  // ping-pong node buffers: level 1 -> recA, 2 -> recB, 3 -> recA, ...
-  uint8_t* bufs[2] = {a.rec_a, a.rec_b};
-  {
-    const long total = a.nsq * 2L * w * (w / 2);
-    hipLaunchKernelGGL(nmt_level1_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a,
-                       bufs[0], (int)(levels == 1));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
-  for (int L = 2; L <= levels; L++) {
+  const int levels = nmt_levels(a.k);
+  if (first < 1 || last > levels || first > last) return hipErrorInvalidValue;
+  for (int L = first; L <= last; L++) {
+    const uint8_t* in = pp[(L - first) & 1];
+    uint8_t* out = L == last && last_out ? last_out : pp[(L - first + 1) & 1];
     const long total = a.nsq * 2L * w * (w >> L);
-    hipLaunchKernelGGL(nmt_level_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a,
-                       (const uint8_t*)bufs[(L - 2) & 1], bufs[(L - 1) & 1], L, (int)(L == levels));
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (L == 1)
+      hipLaunchKernelGGL(nmt_level1_kernel, grid, dim3(256), 0, s, a, out, (int)(levels == 1));
+    else
+      hipLaunchKernelGGL(nmt_level_kernel, grid, dim3(256), 0, s, a, in, out, L, (int)(L == levels));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
 }
 
-static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-size_t nmt_workspace_bytes(int k, long nsq) {
-  const size_t w = 2 * (size_t)k;
-  const size_t dig = align256(w * w * kDigest * nsq);
-  const size_t ns = align256((size_t)k * k * 32 * nsq);
-  const size_t ra = align256(nsq * 2 * w * (w / 2) * 48);
-  const size_t rb = align256(nsq * 2 * w * (w / 4 > 0 ? w / 4 : 1) * 48);
-  return dig + ns + ra + rb;
+hipError_t launch_nmt_trees(const SquareArgs& a, hipStream_t s) {
+  // ping-pong node buffers: level 1 -> recA, 2 -> recB, 3 -> recA, ...
+  uint8_t* const pp[2] = {a.rec_b, a.rec_a};
+  return launch_nmt_tree_levels(a, 1, nmt_levels(a.k), pp, nullptr, s);
 }
+
+long nmt_level_fill_blocks() {
+  static const long fill = [] {
+    int dev = 0, cus = 0, per_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nmt_level_kernel, 256, 0) != hipSuccess ||
+        cus <= 0 || per_cu <= 0) {
+      (void)hipGetLastError();
+      return 0L;  // unknown: defer nothing
+    }
+    return (long)cus * per_cu;
+  }();
+  return fill;
+}
+
+static size_t align256(size_t v) { return ws_align256(v); }
+
+size_t nmt_workspace_bytes(int k, long nsq) { return nmt_ws_bytes(k, nsq); }
 
 void nmt_workspace_carve(SquareArgs& a, void* ws) {
   const size_t w = 2 * (size_t)a.k;

@@ -118,7 +118,10 @@ int dagpu_host_unregister(void* p);
  * memory; work is enqueued on `stream` (hipStream_t, NULL = default stream) and
  * the call returns without synchronising.  d_ods may be NULL when Q0 is already
  * in place inside d_eds.  d_status: n int32 bitmasks (0 = OK, 1 = push order).
- * d_workspace: dagpu_workspace_size(k, n) bytes. */
+ * d_workspace: dagpu_workspace_size(k, n) bytes.  Every output (EDS, roots,
+ * DAHs, status) is complete only when `stream` reaches the end of the call's
+ * work: a large batch is hashed in slices, and the DAHs of all squares, the
+ * first ones included, are written by the call's last launch. */
 size_t dagpu_workspace_size(uint32_t k, size_t n);
 int dagpu_extend_batch_device(dagpu_ctx* ctx, uint32_t k, size_t n, const uint8_t* d_ods,
                               uint8_t* d_eds, uint8_t* d_row_roots, uint8_t* d_col_roots,

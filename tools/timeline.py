@@ -1,8 +1,9 @@
 """Summarise a rocprofv3 kernel_trace.csv of bench.py: the DA kernels of one
 timed step as a timeline relative to its first dispatch.  Steps run back to
-back; with S pipeline slices a step is S x (2 RS + leaves + tree levels + DAH)
-dispatches.  Usage: timeline.py kernel_trace.csv [step index, default 1 of the
-timed run] [dispatches per step, default 48 = 4 slices at k = 128]"""
+back; with S pipeline slices a step is S x (2 RS + 2 leaf halves + tree levels
+1..cut) + the deferred tree levels + 1 DAH dispatches.  Usage: timeline.py
+kernel_trace.csv [step index, default 2] [dispatches per step, default 62 =
+8 slices at k = 128 with cut = 3; 48 for builds before the batch-wide tail]"""
 import csv
 import sys
 
@@ -16,7 +17,7 @@ with open(sys.argv[1]) as f:
                      n.split("(")[0].replace("dagpu::", "").replace("void ", ""), r.get("Queue_Id", "")))
 rows.sort()
 step = int(sys.argv[2]) if len(sys.argv) > 2 else 2
-per = int(sys.argv[3]) if len(sys.argv) > 3 else 48
+per = int(sys.argv[3]) if len(sys.argv) > 3 else 62
 seg = rows[step * per:(step + 1) * per]
 if not seg:
     n_steps = len(rows) // per if per else 0
