@@ -87,7 +87,15 @@ EXPORTS = (
     "dagpu_row_nodes_workspace_size",
     "dagpu_row_nodes_device",
     "dagpu_row_nodes_gather_device",
+    "dagpu_col_nodes_size",
+    "dagpu_col_nodes_workspace_size",
+    "dagpu_col_nodes_device",
+    "dagpu_nmt_prove_workspace_size",
+    "dagpu_nmt_prove_batch_device",
 )
+
+PROVE_REQ_WORDS = 4
+NMT_DESC_WORDS = 8
 
 PREFIX_NONE = 0
 PREFIX_SELF = 1
@@ -217,6 +225,15 @@ def lib() -> ctypes.CDLL:
         L.dagpu_row_nodes_workspace_size.restype = sz
         L.dagpu_row_nodes_device.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp]
         L.dagpu_row_nodes_gather_device.argtypes = [vp, ctypes.c_uint32, vp, sz, vp, vp, vp]
+        L.dagpu_col_nodes_size.argtypes = [ctypes.c_uint32]
+        L.dagpu_col_nodes_size.restype = sz
+        L.dagpu_col_nodes_workspace_size.argtypes = [ctypes.c_uint32]
+        L.dagpu_col_nodes_workspace_size.restype = sz
+        L.dagpu_col_nodes_device.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp]
+        L.dagpu_nmt_prove_workspace_size.argtypes = [sz]
+        L.dagpu_nmt_prove_workspace_size.restype = sz
+        L.dagpu_nmt_prove_batch_device.argtypes = [vp, ctypes.c_uint32, sz, vp, vp, vp, vp, vp, sz, vp, vp, sz, vp,
+                                                   ctypes.POINTER(sz), vp, vp]
         L.dagpu_profile_enable.argtypes = [vp, ctypes.c_int]
         L.dagpu_profile_read.argtypes = [vp, vp, vp, ctypes.c_int]
         _lib = L

@@ -60,6 +60,62 @@ def nmt_verify_batch_device(desc, namespaces: torch.Tensor, leaves: torch.Tensor
     return status
 
 
+def nmt_prove_batch_device(nodes, requests, eds: Optional[torch.Tensor] = None, ctx: Optional[Context] = None,
+                           stream: Optional[torch.cuda.Stream] = None,
+                           workspace: Optional[torch.Tensor] = None):
+    """dagpu_nmt_prove_batch_device: nmt ProveRange for many (axis, index,
+    start, end) requests on the row (axis 0) and column (axis 1) trees of one
+    resident square, enqueued on `stream` (no sync of the results).
+
+    nodes: inclusion.EDSAxisNodes; requests: (n, 4) int64-like on the HOST.
+    With `eds` (the square on the device, e.g. nodes.eds) the proven cells are
+    gathered too.  Returns (proof_nodes, namespaces, shares, desc): uint8 device
+    tensors of 90 B per node, 29 B per proof and 512 B per proven cell (None
+    without `eds`), and the (n, 8) int64 HOST descriptors in the layout
+    nmt_verify_batch_device takes, for a roots table cat(row_roots, col_roots).
+    namespaces[i] is the namespace of the range's first leaf: a range over
+    several namespaces gets a correct proof that no single namespace verifies
+    (proof.parse_namespace rejects such ranges)."""
+    import ctypes
+
+    import numpy as np
+    c = ctx or nodes.ctx
+    req = np.ascontiguousarray(np.asarray(requests, dtype=np.int64).reshape(-1, _abi.PROVE_REQ_WORDS))
+    n = int(req.shape[0])
+    w, dev = nodes.w, nodes.nodes.device
+    if eds is not None and (eds.dtype != torch.uint8 or eds.device != dev or not eds.is_contiguous()
+                            or eds.numel() != w * w * 512):
+        raise ValueError("eds must be the contiguous (2k)^2 x 512 uint8 square on the nodes' device")
+    # capacities from the requests as given; the library validates them
+    m = w.bit_length() - 1
+    start, last = req[:, 2].clip(0, w), (req[:, 3] - 1).clip(0, w - 1)
+
+    def popcount(v):
+        return np.unpackbits(v.astype(">u4").view(np.uint8)).reshape(len(v), 32).sum(axis=1)
+
+    # popcount(start) + log2(2k) - popcount(end - 1) nodes per proof
+    nodes_cap = int((popcount(start) + m - popcount(last)).sum()) if n else 0
+    shares_cap = int((req[:, 3] - req[:, 2]).clip(0, w).sum()) if eds is not None else 0
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.stream(s):
+        out_nodes = torch.empty((nodes_cap * ROOT,), dtype=torch.uint8, device=dev)
+        out_ns = torch.empty((n * 29,), dtype=torch.uint8, device=dev)
+        out_shares = torch.empty((shares_cap * 512,), dtype=torch.uint8, device=dev) if eds is not None else None
+        if workspace is None:
+            workspace = torch.empty((c._L.dagpu_nmt_prove_workspace_size(n),), dtype=torch.uint8, device=dev)
+    if workspace.numel() < c._L.dagpu_nmt_prove_workspace_size(n):
+        raise ValueError("workspace smaller than dagpu_nmt_prove_workspace_size")
+    desc = np.zeros((n, _abi.NMT_DESC_WORDS), np.int64)
+    total = ctypes.c_size_t(0)
+    rc = c._L.dagpu_nmt_prove_batch_device(
+        c.handle, nodes.k, n, _abi.addr(req), _abi.addr(eds), _abi.addr(nodes.nodes), _abi.addr(nodes.col_inner),
+        _abi.addr(out_nodes), nodes_cap, _abi.addr(out_ns), _abi.addr(out_shares), shares_cap, _abi.addr(desc),
+        ctypes.byref(total), _abi.addr(workspace), _stream_handle(s))
+    if rc != 0:
+        raise DAError(rc, c.last_error())
+    return out_nodes[:total.value * ROOT], out_ns, out_shares, desc
+
+
 class DeviceSquares:
     """n squares of width k resident on one GPU.
 

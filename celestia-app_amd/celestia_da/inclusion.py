@@ -204,6 +204,45 @@ class EDSSubTreeRootCacher:
         return self.get_sub_tree_roots(dah, [Path(list(path), row)])[0]
 
 
+class EDSAxisNodes:
+    """Every node of every row tree AND column tree of one EDS, resident in
+    HBM: the row store of dagpu_row_nodes_device (its level 0 holds the leaf
+    nodes of both axes) plus the column trees' inner levels
+    (dagpu_col_nodes_device).  What device.nmt_prove_batch_device and
+    proof.prove_ranges select proof nodes from; the square itself stays
+    referenced as `eds` for the share gather.
+
+    Built from an EDS already on the device or from host bytes (uploaded once)."""
+
+    def __init__(self, k: int, eds, ctx: Optional[Context] = None, device: int = 0):
+        self.ctx = ctx or default_context()
+        self.k = k
+        self.w = 2 * k
+        L = self.ctx._L
+        if isinstance(eds, torch.Tensor) and eds.is_cuda:
+            d_eds = eds.reshape(-1)
+        else:
+            d_eds = torch.from_numpy(np.ascontiguousarray(eds, dtype=np.uint8).reshape(-1)).to(
+                torch.device("cuda", device))
+        if d_eds.numel() != self.w * self.w * 512:
+            raise DAError(_abi.ERR_ARG, "EDS size does not match k")
+        self.eds = d_eds
+        dev = d_eds.device
+        self.nodes = torch.empty(L.dagpu_row_nodes_size(k), dtype=torch.uint8, device=dev)
+        self.col_inner = torch.empty(L.dagpu_col_nodes_size(k), dtype=torch.uint8, device=dev)
+        ws = torch.empty(max(L.dagpu_row_nodes_workspace_size(k), L.dagpu_col_nodes_workspace_size(k)),
+                         dtype=torch.uint8, device=dev)
+        s = torch.cuda.current_stream(dev).cuda_stream
+        self.ctx.check(L.dagpu_row_nodes_device(self.ctx.handle, k, d_eds.data_ptr(), self.nodes.data_ptr(),
+                                                ws.data_ptr(), s))
+        self.ctx.check(L.dagpu_col_nodes_device(self.ctx.handle, k, self.nodes.data_ptr(),
+                                                self.col_inner.data_ptr(), ws.data_ptr(), s))
+
+    def col_roots(self) -> torch.Tensor:
+        """(2k, 96) view of the column roots: the top level of the column store."""
+        return self.col_inner.view(-1, 96)[-self.w:]
+
+
 def get_commitment(cacher: EDSSubTreeRootCacher, dah: DataAvailabilityHeader, start: int,
                    blob_share_len: int,
                    subtree_root_threshold: int = DEFAULT_SUBTREE_ROOT_THRESHOLD) -> bytes:

@@ -464,6 +464,21 @@ def prove_row_ranges(cacher: EDSSubTreeRootCacher, ranges: Sequence[Tuple[int, i
     return [NMTProof(s, e, got[a:a + n]) for (row, s, e), (a, n) in zip(ranges, spans)]
 
 
+def prove_ranges(axis_nodes, requests: Sequence[Tuple[int, int, int, int]]) -> List[NMTProof]:
+    """ProveRange(start, end) on row (axis 0) and column (axis 1) trees of one
+    resident square: requests = (axis, index, start, end), axis_nodes an
+    inclusion.EDSAxisNodes.  One dagpu_nmt_prove_batch_device call and one copy
+    to the host for the whole list; range_proof_nodes / prove_row_ranges stay
+    the specification of the node order."""
+    from .device import nmt_prove_batch_device
+    if not len(requests):
+        return []
+    nodes, _, _, desc = nmt_prove_batch_device(axis_nodes, requests)
+    host = nodes.cpu().numpy().tobytes()
+    return [NMTProof(int(d[0]), int(d[1]), [host[90 * j:90 * (j + 1)] for j in range(int(d[5]), int(d[5] + d[4]))])
+            for d in desc]
+
+
 def new_share_inclusion_proof(shares: Sequence[bytes], namespace: bytes, share_range: Tuple[int, int],
                               ctx: Optional[Context] = None) -> ShareProof:
     """NewShareInclusionProof for a data square given as its k*k shares;

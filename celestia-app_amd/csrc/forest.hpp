@@ -77,6 +77,27 @@ hipError_t launch_node_to_rec(const uint8_t* nodes, long n, uint8_t* recs, hipSt
 hipError_t launch_node_gather(const uint8_t* nodes, int w, const uint32_t* req, long n, uint8_t* out,
                               hipStream_t s);
 
+// Batched range proofs from the exported trees of one square (nmt_prove.hip).
+// Everything the host validated and laid out (prove_layout.hpp); the kernels
+// check nothing.
+struct ProveArgs {
+  long n;                   // proofs
+  int w, logw;              // leaves per tree (2k) and log2 of it
+  const uint64_t* req;      // n packed requests (prove_pack_req)
+  const int64_t* node_off;  // n + 1 prefix sums: first output node of proof i
+  const int64_t* leaf_off;  // n + 1 prefix sums: first output cell of proof i
+  long n_nodes, n_leaves;   // node_off[n], leaf_off[n]
+  const uint8_t* row_nodes; // dagpu_row_nodes_device store (96-B records)
+  const uint8_t* col_inner; // dagpu_col_nodes_device store, null without axis-1 requests
+  const uint8_t* eds;       // the square, for the share gather
+  uint8_t* nodes_out;       // n_nodes packed 90-B nodes
+  uint8_t* ns_out;          // n x 29 B
+  uint8_t* shares_out;      // n_leaves x 512 B
+};
+hipError_t launch_prove_emit(const ProveArgs& a, hipStream_t s);
+hipError_t launch_prove_namespaces(const ProveArgs& a, hipStream_t s);
+hipError_t launch_prove_shares(const ProveArgs& a, hipStream_t s);
+
 // Host-side level plan of one forest.  Leaves (level 0) are either packed tree
 // after tree (ragged: counts[t] leaves each) or uniform with (tstride,
 // lstride) addressing inside a caller-owned leaf array.  Levels >= 1 are packed

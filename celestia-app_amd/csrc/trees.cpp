@@ -14,6 +14,11 @@
 //                          for many proofs (celestia-core ShareProof.Validate /
 //                          RowProof.Validate; consumer x/blobstream/client/verify.go:216-227),
 //                          hashed on the device (proof_verify.hip)
+//   dagpu_col_nodes_device / dagpu_nmt_prove_batch_device
+//                          nmt ProveRange for many requests on the row and column
+//                          trees of a resident square (pkg/proof/proof.go:87-150),
+//                          nodes selected on the device (nmt_prove.hip); request
+//                          checks and layout in prove_layout.hpp
 // Each call uploads the pushes once, hashes every leaf and level of every
 // tree in a handful of launches (nmt_forest.hip) and returns the roots.
 #include <hip/hip_runtime.h>
@@ -30,6 +35,7 @@
 #include "kernels.hpp"
 #include "host_sha256.hpp"
 #include "proof_verify.hpp"
+#include "prove_layout.hpp"
 #include "runtime.hpp"
 
 namespace {
@@ -367,6 +373,96 @@ int dagpu_row_nodes_gather_device(dagpu_ctx* ctx, uint32_t k, const uint8_t* d_n
   int rc = check_k(ctx, k);
   if (rc) return rc;
   HIP_TRY(ctx, launch_node_gather(d_nodes, 2 * (int)k, d_requests, (long)n, d_out, (hipStream_t)stream));
+  return DAGPU_OK;
+}
+
+size_t dagpu_col_nodes_size(uint32_t k) {
+  const size_t rows = dagpu_row_nodes_size(k);
+  return rows ? rows - (size_t)(2L * k) * (size_t)(2L * k) * kRecNmt : 0;
+}
+
+size_t dagpu_col_nodes_workspace_size(uint32_t k) {
+  if (k == 0 || !is_pow2(k) || k > (uint32_t)kMaxK) return 0;
+  return 256;  // the uniform plan addresses its levels by shape: nothing is uploaded
+}
+
+int dagpu_col_nodes_device(dagpu_ctx* ctx, uint32_t k, const uint8_t* d_row_nodes, uint8_t* d_col_inner,
+                           void* d_workspace, void* stream) {
+  if (!ctx || !d_row_nodes || !d_col_inner || !d_workspace) return DAGPU_ERR_ARG;
+  int rc = check_k(ctx, k);
+  if (rc) return rc;
+  if (((uintptr_t)d_row_nodes | (uintptr_t)d_col_inner) & 15)
+    return set_err(ctx, DAGPU_ERR_ARG, "dagpu_col_nodes_device: node stores must be 16-B aligned");
+  hipStream_t s = (hipStream_t)stream;
+  const long w = 2L * k;
+  // every column tree over the row store's leaf records (tree c: leaf r at
+  // r * w + c), all inner levels kept; the top level is the column roots
+  ForestPlan plan = ForestPlan::uniform_plan(w, w, 1, w);
+  HIP_TRY(ctx, forest_enqueue(plan, d_row_nodes, d_col_inner, (int64_t*)d_workspace, 1, 0, 0, nullptr,
+                              d_col_inner + (size_t)plan.base[plan.nlevels] * kRecNmt, 1, 0, s));
+  return DAGPU_OK;
+}
+
+size_t dagpu_nmt_prove_workspace_size(size_t n) {
+  // packed requests (n) | node_off (n + 1) | leaf_off (n + 1), 8 B each
+  return align256((3 * n + 2) * sizeof(int64_t)) + 256;
+}
+
+int dagpu_nmt_prove_batch_device(dagpu_ctx* ctx, uint32_t k, size_t n, const int64_t* req, const uint8_t* d_eds,
+                                 const uint8_t* d_row_nodes, const uint8_t* d_col_inner, uint8_t* d_nodes_out,
+                                 size_t nodes_cap, uint8_t* d_ns_out, uint8_t* d_shares_out, size_t shares_cap,
+                                 int64_t* desc_out, size_t* n_nodes_total, void* d_workspace, void* stream) {
+  if (!ctx) return DAGPU_ERR_ARG;
+  int rc = check_k(ctx, k);
+  if (rc) return rc;
+  if (n == 0) {
+    if (n_nodes_total) *n_nodes_total = 0;
+    return DAGPU_OK;
+  }
+  if (!req || !d_row_nodes || !d_workspace || (nodes_cap && !d_nodes_out) || (d_shares_out && !d_eds))
+    return set_err(ctx, DAGPU_ERR_ARG, "dagpu_nmt_prove_batch_device: null buffer");
+  if ((((uintptr_t)d_workspace | (uintptr_t)d_row_nodes | (uintptr_t)d_col_inner | (uintptr_t)d_eds |
+        (uintptr_t)d_shares_out) & 15) != 0 || (((uintptr_t)d_nodes_out) & 1) != 0)
+    return set_err(ctx, DAGPU_ERR_ARG, "dagpu_nmt_prove_batch_device: misaligned buffer");
+  ProveLayout lay;
+  size_t bad = 0;
+  const ProveCheck pc = prove_layout(k, n, req, d_col_inner != nullptr, nodes_cap, d_shares_out != nullptr,
+                                     shares_cap, &lay, &bad);
+  if (pc != kProveOk) {
+    static const char* const why[] = {"", "axis is not 0 or 1", "index outside the square",
+                                      "range is not 0 <= start < end <= 2k", "column request without column nodes",
+                                      "more proof nodes than nodes_cap", "more proven cells than shares_cap"};
+    return set_err(ctx, DAGPU_ERR_ARG,
+                   (bad < n ? "proof request " + std::to_string(bad) + ": " : std::string("proof batch: ")) + why[pc]);
+  }
+  // device image: packed requests, then the two offset arrays
+  std::vector<int64_t> meta(3 * n + 2);
+  for (size_t i = 0; i < n; i++) meta[i] = (int64_t)prove_pack_req(req + i * kProveReqWords);
+  memcpy(meta.data() + n, lay.node_off.data(), (n + 1) * sizeof(int64_t));
+  memcpy(meta.data() + 2 * n + 1, lay.leaf_off.data(), (n + 1) * sizeof(int64_t));
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(ctx, hipMemcpyAsync(d_workspace, meta.data(), meta.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
+  HIP_TRY(ctx, hipStreamSynchronize(s));  // `meta` and the caller's requests may go
+  ProveArgs a{};
+  a.n = (long)n;
+  a.w = 2 * (int)k;
+  a.logw = prove_log2(2 * k);
+  a.req = (const uint64_t*)d_workspace;
+  a.node_off = (const int64_t*)d_workspace + n;
+  a.leaf_off = a.node_off + (n + 1);
+  a.n_nodes = (long)lay.n_nodes;
+  a.n_leaves = (long)lay.n_leaves;
+  a.row_nodes = d_row_nodes;
+  a.col_inner = d_col_inner;
+  a.eds = d_eds;
+  a.nodes_out = d_nodes_out;
+  a.ns_out = d_ns_out;
+  a.shares_out = d_shares_out;
+  HIP_TRY(ctx, launch_prove_emit(a, s));
+  if (d_ns_out) HIP_TRY(ctx, launch_prove_namespaces(a, s));
+  if (d_shares_out) HIP_TRY(ctx, launch_prove_shares(a, s));
+  if (desc_out) prove_fill_desc(k, n, req, lay, desc_out);
+  if (n_nodes_total) *n_nodes_total = (size_t)lay.n_nodes;
   return DAGPU_OK;
 }
 

@@ -466,6 +466,82 @@ int dagpu_row_nodes_device(dagpu_ctx* ctx, uint32_t k, const uint8_t* d_eds, uin
 int dagpu_row_nodes_gather_device(dagpu_ctx* ctx, uint32_t k, const uint8_t* d_nodes, size_t n,
                                   const uint32_t* d_requests, uint8_t* d_out, void* stream);
 
+/* ---- Column-tree inner nodes ----------------------------------------------
+ * The DAH commits to the column roots as well as the row roots, and rsmt2d /
+ * celestia-node samples and the shares of a bad-encoding fraud proof are
+ * proven against a column root.  The leaf node of cell (r, c) is the same in
+ * row tree r and in column tree c (the wrapper's namespace prefix depends only
+ * on Q0 membership), so level 0 of the row store above is level 0 of the column
+ * trees too: leaf r of column c is record r*2k + c, and no leaf is hashed twice.
+ * dagpu_col_nodes_device hashes levels 1 .. log2(2k) of every column tree from
+ * d_row_nodes (a store filled by dagpu_row_nodes_device) into d_col_inner
+ * (dagpu_col_nodes_size(k) = dagpu_row_nodes_size(k) - (2k)^2*96 bytes), the
+ * same 96-B records: node (col, L, p), L >= 1, is record
+ * sum_{1<=l<L} 2k*(2k>>l) + col*(2k>>L) + p; the level-log2(2k) nodes are the
+ * column roots.  Both stores 16-B aligned.  Unlike the row call it only
+ * ENQUEUES on `stream` and does not synchronise (nothing is uploaded);
+ * d_workspace (dagpu_col_nodes_workspace_size(k) bytes) is reserved. */
+size_t dagpu_col_nodes_size(uint32_t k);
+size_t dagpu_col_nodes_workspace_size(uint32_t k);
+int dagpu_col_nodes_device(dagpu_ctx* ctx, uint32_t k, const uint8_t* d_row_nodes, uint8_t* d_col_inner,
+                           void* d_workspace, void* stream);
+
+/* ---- Many nmt range proofs produced in one call ---------------------------
+ * nmt ProveRange(start, end) on row or column trees of one resident square
+ * (what pkg/proof/proof.go:87-150 asks of the wrapper tree row by row), for a
+ * whole list of requests, written in the layout dagpu_nmt_verify_batch_device
+ * takes: produce -> verify or produce -> ship needs no host step.  Nothing is
+ * hashed: a proof is a selection of nodes of the two stores above.
+ *
+ * A request is one fixed record of int64 in HOST memory:
+ *   req[4i..] = { axis (0 row, 1 column), index, start, end }
+ * The nodes of [start, end) in a tree of 2k = 2^m leaves are the roots of the
+ * maximal subtrees disjoint from the range, left to right (nmt
+ * buildRangeProof): for each set bit b of start from high to low the node at
+ * depth m-b, position (start>>b)-1; then for each zero bit b of end-1 from
+ * b = 0 up the node at depth m-b, position ((end-1)>>b)+1;
+ * popcount(start) + m - popcount(end-1) nodes, none for [0, 2k).
+ *
+ * Outputs, proof after proof in request order with no gaps:
+ *   d_nodes_out   packed 90-B nodes (2-B aligned), nodes_cap = capacity in nodes
+ *   d_ns_out      optional, n x 29 B: the min-namespace of the range's FIRST
+ *                 leaf (share[0:29] inside Q0, 0xFF x 29 elsewhere)
+ *   d_shares_out  optional, the proven cells, 512 B each (16-B aligned, as
+ *                 d_eds), shares_cap = capacity in cells; d_eds is read only
+ *                 for these and may be NULL when d_shares_out is NULL
+ *   desc_out      optional, HOST, n x DAGPU_NMT_DESC_WORDS: { start, end,
+ *                 n_leaves = end-start, leaf_off, n_nodes, node_off,
+ *                 ns_index = i, root_index = axis*2k + index }, i.e. leaves in
+ *                 d_shares_out, namespaces in d_ns_out and a roots table
+ *                 row_roots || col_roots (4k x 90 B).  A single-cell row sample
+ *                 may instead point leaf_off at the EDS itself
+ *                 (index*2k + start), as the verifier allows.
+ *   *n_nodes_total (optional) the nodes written.
+ * Namespaces: VerifyInclusion prepends ONE namespace to every leaf of a proof,
+ * so a range that spans several namespaces gets a correct proof that no single
+ * namespace verifies; the reference's ParseNamespace (pkg/proof/querier.go)
+ * rejects such ranges before proving, and callers should do the same.
+ *
+ * Every request is checked before anything is launched: axis not 0 / 1, index
+ * outside [0, 2k), not 0 <= start < end <= 2k, an axis-1 request with
+ * d_col_inner == NULL, more nodes than nodes_cap or (with d_shares_out) more
+ * cells than shares_cap fails the whole call with DAGPU_ERR_ARG and leaves
+ * every output, desc_out and *n_nodes_total included, untouched.
+ *
+ * Stream contract as dagpu_nmt_verify_batch_device: d_workspace (16-B aligned)
+ * of dagpu_nmt_prove_workspace_size(n) bytes; the call returns when requests
+ * and offsets are uploaded (it waits for `stream` up to that copy, and `req`
+ * may be freed); the kernels are enqueued only, and a verify call on the same
+ * stream may follow with no synchronisation. */
+#define DAGPU_PROVE_REQ_WORDS 4
+size_t dagpu_nmt_prove_workspace_size(size_t n);
+int dagpu_nmt_prove_batch_device(dagpu_ctx* ctx, uint32_t k, size_t n, const int64_t* req,
+                                 const uint8_t* d_eds, const uint8_t* d_row_nodes,
+                                 const uint8_t* d_col_inner, uint8_t* d_nodes_out, size_t nodes_cap,
+                                 uint8_t* d_ns_out, uint8_t* d_shares_out, size_t shares_cap,
+                                 int64_t* desc_out, size_t* n_nodes_total, void* d_workspace,
+                                 void* stream);
+
 /* ---- Square construction (host; pkg/square, app version 1) ---------------
  * square.Construct (pkg/square/square.go:22-63, builder.go): ntx txs packed
  * back to back in `txs` (tx_lens[i] bytes each; blob txs in the BlobTx proto
