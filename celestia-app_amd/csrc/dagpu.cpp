@@ -16,6 +16,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <map>
 #include <mutex>
@@ -1781,3 +1782,30 @@ int dagpu_dah_hash(const uint8_t* row_roots, const uint8_t* col_roots, size_t w,
 }
 
 }  // extern "C"
+
+#ifdef DAGPU_TEST_HOOKS
+// Test build only (libdagpu_test.so, tests/test_gpu_rs_arms.py): launches per
+// GF(2^8) kernel arm (kernels.hpp RsArm), counted by the dispatchers.
+namespace dagpu {
+namespace {
+std::atomic<uint64_t> g_rs_arms[ARM_COUNT * kRsArmKs];
+}
+void rs_arm_launched(RsArm arm, int k) {
+  int lg = 0;
+  while ((1 << lg) < k && lg < kRsArmKs - 1) lg++;
+  g_rs_arms[(int)arm * kRsArmKs + lg].fetch_add(1, std::memory_order_relaxed);
+}
+}  // namespace dagpu
+
+// counts[arm * 8 + log2(k)] for the first n of the ARM_COUNT * 8 counters;
+// reset != 0 zeroes all of them.  Returns the number of counters.
+extern "C" int dagpu_test_rs_arms(uint64_t* counts, size_t n, int reset) {
+  constexpr size_t total = (size_t)ARM_COUNT * kRsArmKs;
+  for (size_t i = 0; i < total; i++) {
+    const uint64_t c = reset ? g_rs_arms[i].exchange(0, std::memory_order_relaxed)
+                             : g_rs_arms[i].load(std::memory_order_relaxed);
+    if (counts && i < n) counts[i] = c;
+  }
+  return (int)total;
+}
+#endif

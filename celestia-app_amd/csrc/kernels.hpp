@@ -100,6 +100,33 @@ __device__ __forceinline__ bool vec_skipped(const EncodeArgs& a, long v) {
   return a.vec_flag_match ? f != a.vec_flag_match : f == 0;
 }
 
+// The GF(2^8) kernel arms the dispatchers choose between (launch_leo8_encode,
+// launch_leo8_encode_sliced, launch_leo8_fill_sliced, launch_leo8_decode_only).
+// Test builds only (DAGPU_TEST_HOOKS, libdagpu_test.so): every launch of an
+// arm counts in a host-side table, counts[arm * kRsArmKs + log2(k)], read by
+// dagpu_test_rs_arms (dagpu.cpp), so a test that sets a switch can tell which
+// kernel ran (tests/test_gpu_rs_arms.py).  The product build counts nothing
+// and carries no reader.
+enum RsArm : int {
+  ARM_ENC_PACKED,      // leo8_encode_kernel<K, false>
+  ARM_ENC_PACKED_REV,  // leo8_encode_kernel<K, true>
+  ARM_ENC_SLICED4,     // leo8_encode_sliced_kernel<K>
+  ARM_ENC_SLICED2,     // leo8_encode_sliced2_kernel<false>
+  ARM_FILL_SLICED2,    // leo8_encode_sliced2_kernel<true, false>
+  ARM_FILL_SLICED2_REV,  // leo8_encode_sliced2_kernel<true, true>
+  ARM_DEC_SMALL,       // leo8_decode_kernel<K>
+  ARM_DEC_PACKED128,   // leo8_decode128_kernel
+  ARM_DEC_SLICED128,   // leo8_decode128_sliced_kernel
+  ARM_COUNT
+};
+constexpr int kRsArmKs = 8;  // k = 1, 2, .., 128
+#ifdef DAGPU_TEST_HOOKS
+void rs_arm_launched(RsArm arm, int k);
+#define DAGPU_RS_ARM(arm, k) ::dagpu::rs_arm_launched(arm, k)
+#else
+#define DAGPU_RS_ARM(arm, k) ((void)0)
+#endif
+
 hipError_t launch_leo8_encode(int k, const EncodeArgs& a, hipStream_t s);
 // bit-sliced GF(2^8) encode (rs_gf8_sliced.hip); launch_leo8_encode uses it
 // whenever leo8_sliced_applicable() holds

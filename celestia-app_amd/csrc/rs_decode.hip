@@ -444,6 +444,7 @@ __global__ __launch_bounds__(256) void mark_present_kernel(DecodeArgs a) {
 template <int K>
 static hipError_t launch_dec(const DecodeArgs& a, hipStream_t s) {
   const long blocks = a.nsq * a.nvec * a.nchunk;
+  DAGPU_RS_ARM(ARM_DEC_SMALL, K);
   hipLaunchKernelGGL((leo8_decode_kernel<K>), dim3((unsigned)blocks), dim3(128), 0, s, a);
   return hipGetLastError();
 }
@@ -470,10 +471,12 @@ hipError_t launch_leo8_decode_only(const DecodeArgs& a, hipStream_t s, bool mark
     case 64: e = launch_dec<64>(a, s); break;
     case 128: {
       if (leo8_decode_sliced_applicable(a)) {
+        DAGPU_RS_ARM(ARM_DEC_SLICED128, 128);
         e = launch_leo8_decode128_sliced(a, s);
         break;
       }
       const long nc = (a.shard_bytes + 255) / 256;
+      DAGPU_RS_ARM(ARM_DEC_PACKED128, 128);
       hipLaunchKernelGGL(leo8_decode128_kernel, dim3((unsigned)(nv * nc)), dim3(kD4Threads), 0, s, a, (int)nc);
       e = hipGetLastError();
       break;

@@ -239,8 +239,10 @@ static hipError_t launch_k(const EncodeArgs& a, hipStream_t s) {
   if (blocks <= 0) return hipSuccess;
   if (a.reverse) {
     if (!a.out_present) return hipErrorInvalidValue;  // reverse transform: Repair fill only
+    DAGPU_RS_ARM(ARM_ENC_PACKED_REV, K);
     hipLaunchKernelGGL((leo8_encode_kernel<K, true>), dim3((unsigned)blocks), dim3(128), 0, s, a);
   } else {
+    DAGPU_RS_ARM(ARM_ENC_PACKED, K);
     hipLaunchKernelGGL((leo8_encode_kernel<K, false>), dim3((unsigned)blocks), dim3(128 * EncSplit<K>::H), 0, s, a);
   }
   return hipGetLastError();

@@ -353,6 +353,7 @@ template <int K>
 static hipError_t launch_sliced_k(const EncodeArgs& a, hipStream_t s) {
   const long blocks = a.nsq * (a.nvec / 4) * a.nchunk;
   if (blocks <= 0) return hipSuccess;
+  DAGPU_RS_ARM(ARM_ENC_SLICED4, K);
   hipLaunchKernelGGL(leo8_encode_sliced_kernel<K>, dim3((unsigned)blocks), dim3(64 * Geo<K>::NW), 0, s, a);
   return hipGetLastError();
 }
@@ -396,6 +397,7 @@ hipError_t launch_leo8_encode_sliced(int k, const EncodeArgs& a, hipStream_t s) 
   if (k == 128 && sliced2_enabled()) {
     const long blocks = a.nsq * (a.nvec / 2) * a.nchunk;
     if (blocks <= 0) return hipSuccess;
+    DAGPU_RS_ARM(ARM_ENC_SLICED2, 128);
     hipLaunchKernelGGL(leo8_encode_sliced2_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, a);
     return hipGetLastError();
   }
@@ -426,6 +428,7 @@ bool leo8_fill_sliced_applicable(const EncodeArgs& a) {
 hipError_t launch_leo8_fill_sliced(const EncodeArgs& a, long max_pairs, hipStream_t s) {
   const long blocks = max_pairs * a.nchunk;
   if (blocks <= 0) return hipSuccess;
+  DAGPU_RS_ARM(a.reverse ? ARM_FILL_SLICED2_REV : ARM_FILL_SLICED2, 128);
   if (a.reverse) hipLaunchKernelGGL((leo8_encode_sliced2_kernel<true, true>), dim3((unsigned)blocks), dim3(256), 0, s, a);
   else hipLaunchKernelGGL((leo8_encode_sliced2_kernel<true, false>), dim3((unsigned)blocks), dim3(256), 0, s, a);
   return hipGetLastError();
