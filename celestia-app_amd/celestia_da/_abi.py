@@ -92,10 +92,19 @@ EXPORTS = (
     "dagpu_col_nodes_device",
     "dagpu_nmt_prove_workspace_size",
     "dagpu_nmt_prove_batch_device",
+    "dagpu_nmt_verify_namespace",
+    "dagpu_nmt_verify_namespace_batch",
+    "dagpu_nmt_verify_namespace_workspace_size",
+    "dagpu_nmt_verify_namespace_batch_device",
+    "dagpu_nmt_namespace_workspace_size",
+    "dagpu_nmt_namespace_ranges_device",
+    "dagpu_nmt_prove_namespace_batch_device",
 )
 
 PROVE_REQ_WORDS = 4
 NMT_DESC_WORDS = 8
+NMT_NS_DESC_WORDS = 9
+NS_OUTSIDE, NS_PRESENT, NS_ABSENT = 0, 1, 2
 
 PREFIX_NONE = 0
 PREFIX_SELF = 1
@@ -234,6 +243,17 @@ def lib() -> ctypes.CDLL:
         L.dagpu_nmt_prove_workspace_size.restype = sz
         L.dagpu_nmt_prove_batch_device.argtypes = [vp, ctypes.c_uint32, sz, vp, vp, vp, vp, vp, sz, vp, vp, sz, vp,
                                                    ctypes.POINTER(sz), vp, vp]
+        L.dagpu_nmt_verify_namespace.argtypes = [vp, vp, sz, sz, i64, i64, vp, sz, vp, vp]
+        L.dagpu_nmt_verify_namespace_batch.argtypes = [vp, sz, vp, vp, sz, vp, sz, sz, vp, sz, vp, sz, vp, sz, vp]
+        L.dagpu_nmt_verify_namespace_workspace_size.argtypes = [sz, sz]
+        L.dagpu_nmt_verify_namespace_workspace_size.restype = sz
+        L.dagpu_nmt_verify_namespace_batch_device.argtypes = [vp, sz, vp, vp, sz, vp, sz, sz, vp, sz, vp, sz, vp, sz,
+                                                              vp, vp, vp]
+        L.dagpu_nmt_namespace_workspace_size.argtypes = [ctypes.c_uint32, sz]
+        L.dagpu_nmt_namespace_workspace_size.restype = sz
+        L.dagpu_nmt_namespace_ranges_device.argtypes = [vp, ctypes.c_uint32, sz, vp, vp, vp, vp, vp, vp]
+        L.dagpu_nmt_prove_namespace_batch_device.argtypes = [vp, ctypes.c_uint32, sz, vp, vp, vp, vp, sz, vp, vp, sz,
+                                                             vp, sz, vp, vp, sz, vp, vp, vp]
         L.dagpu_profile_enable.argtypes = [vp, ctypes.c_int]
         L.dagpu_profile_read.argtypes = [vp, vp, vp, ctypes.c_int]
         _lib = L

@@ -116,6 +116,141 @@ def nmt_prove_batch_device(nodes, requests, eds: Optional[torch.Tensor] = None, 
     return out_nodes[:total.value * ROOT], out_ns, out_shares, desc
 
 
+def _ns_table(namespaces):
+    """(n_q, 29) uint8 HOST array of a list of 29-B namespaces (or such an array)."""
+    import numpy as np
+    if isinstance(namespaces, np.ndarray):
+        q = np.ascontiguousarray(namespaces, dtype=np.uint8).reshape(-1, 29)
+    else:
+        if any(len(n) != 29 for n in namespaces):
+            raise ValueError("namespaces must be 29 bytes each")
+        q = np.frombuffer(b"".join(bytes(n) for n in namespaces), np.uint8).reshape(-1, 29).copy()
+    return q
+
+
+def nmt_namespace_ranges_device(nodes, namespaces, ctx: Optional[Context] = None,
+                                stream: Optional[torch.cuda.Stream] = None,
+                                workspace: Optional[torch.Tensor] = None):
+    """dagpu_nmt_namespace_ranges_device: where every namespace of a list lies
+    in every ROW tree of one resident square (nodes: inclusion.EDSAxisNodes).
+    Returns (ranges, counts): ranges an (n_q, 2k, 3) int32 HOST array of
+    (kind, start, end) with kind _abi.NS_OUTSIDE / NS_PRESENT / NS_ABSENT, counts
+    an int64[4] HOST array (proofs with kind != 0, absence proofs, proof nodes,
+    proven cells).  Synchronises `stream` once."""
+    import numpy as np
+    c = ctx or nodes.ctx
+    q = _ns_table(namespaces)
+    n_q, w, dev = int(q.shape[0]), nodes.w, nodes.nodes.device
+    ranges = np.zeros((n_q, w, 3), np.int32)
+    counts = np.zeros(4, np.int64)
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    need = c._L.dagpu_nmt_namespace_workspace_size(nodes.k, n_q)
+    if workspace is None:
+        with torch.cuda.stream(s):
+            workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+    if workspace.numel() < need:
+        raise ValueError("workspace smaller than dagpu_nmt_namespace_workspace_size")
+    rc = c._L.dagpu_nmt_namespace_ranges_device(c.handle, nodes.k, n_q, _abi.addr(q), _abi.addr(nodes.nodes),
+                                                _abi.addr(ranges), _abi.addr(counts), _abi.addr(workspace),
+                                                _stream_handle(s))
+    if rc != 0:
+        raise DAError(rc, c.last_error())
+    return ranges, counts
+
+
+def nmt_prove_namespace_batch_device(nodes, namespaces, caps=None, ctx: Optional[Context] = None,
+                                     stream: Optional[torch.cuda.Stream] = None,
+                                     workspace: Optional[torch.Tensor] = None):
+    """dagpu_nmt_prove_namespace_batch_device: nmt ProveNamespace of every
+    namespace of a list on every ROW tree of one resident square (nodes:
+    inclusion.EDSAxisNodes, whose `eds` is gathered from), enqueued on `stream`.
+
+    caps = (proofs, nodes, cells, leaf_hashes) sizes the outputs; a capacity too
+    small raises DAError(ERR_ARG) (the library reports the need).  Without caps
+    the need is taken from nmt_namespace_ranges_device first (a second search).
+
+    Returns (proof_nodes, namespaces, shares, leaf_hashes, desc, pairs, counts):
+    uint8 device tensors of 90 B per node, 29 B per query, 512 B per proven cell
+    and 90 B per absence proof; desc the (n, 9) int64 HOST descriptors
+    nmt_verify_namespace_batch_device takes against the row roots (ns_index =
+    query, root_index = row); pairs the (n, 2) int32 HOST (query, row) of each
+    proof; counts as nmt_namespace_ranges_device.  Rows a namespace is outside
+    of have no entry: their proof is the empty proof."""
+    import numpy as np
+    c = ctx or nodes.ctx
+    q = _ns_table(namespaces)
+    n_q, dev = int(q.shape[0]), nodes.nodes.device
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    need = c._L.dagpu_nmt_namespace_workspace_size(nodes.k, n_q)
+    if workspace is None:
+        with torch.cuda.stream(s):
+            workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+    if workspace.numel() < need:
+        raise ValueError("workspace smaller than dagpu_nmt_namespace_workspace_size")
+    if caps is None:
+        caps = nmt_namespace_ranges_device(nodes, q, ctx=c, stream=s, workspace=workspace)[1][[0, 2, 3, 1]]
+    n_p, n_nodes, n_cells, n_lh = (int(v) for v in caps)
+    with torch.cuda.stream(s):
+        out_nodes = torch.empty((n_nodes * ROOT,), dtype=torch.uint8, device=dev)
+        out_ns = torch.empty((n_q * 29,), dtype=torch.uint8, device=dev)
+        out_shares = torch.empty((n_cells * 512,), dtype=torch.uint8, device=dev)
+        out_lh = torch.empty((n_lh * ROOT,), dtype=torch.uint8, device=dev)
+    desc = np.zeros((n_p, _abi.NMT_NS_DESC_WORDS), np.int64)
+    pairs = np.zeros((n_p, 2), np.int32)
+    counts = np.zeros(4, np.int64)
+    rc = c._L.dagpu_nmt_prove_namespace_batch_device(
+        c.handle, nodes.k, n_q, _abi.addr(q), _abi.addr(nodes.eds), _abi.addr(nodes.nodes),
+        _abi.addr(out_nodes) if n_nodes else None, n_nodes, _abi.addr(out_ns) if n_q else None,
+        _abi.addr(out_shares) if n_cells else None, n_cells, _abi.addr(out_lh) if n_lh else None, n_lh,
+        _abi.addr(desc) if n_p else None, _abi.addr(pairs) if n_p else None, n_p, _abi.addr(counts),
+        _abi.addr(workspace), _stream_handle(s))
+    if rc != 0:
+        raise DAError(rc, c.last_error())
+    n = int(counts[0])
+    return (out_nodes[:int(counts[2]) * ROOT], out_ns, out_shares[:int(counts[3]) * 512],
+            out_lh[:int(counts[1]) * ROOT], desc[:n], pairs[:n], counts)
+
+
+def nmt_verify_namespace_batch_device(desc, namespaces: torch.Tensor, leaves: torch.Tensor, leaf_len: int,
+                                      nodes: torch.Tensor, leaf_hashes: torch.Tensor, roots: torch.Tensor,
+                                      ctx: Optional[Context] = None, stream: Optional[torch.cuda.Stream] = None,
+                                      workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dagpu_nmt_verify_namespace_batch_device: nmt Proof.VerifyNamespace
+    (presence with completeness, absence, empty) for many proofs against data
+    already in HBM; returns the (n,) int32 status tensor on the device, enqueued
+    on `stream`.  desc: (n, 9) int64 on the HOST (the eight words of
+    nmt_verify_batch_device plus leaf_hash_index into `leaf_hashes`, 90 B each,
+    -1 = none); the tensors as nmt_verify_batch_device."""
+    import numpy as np
+    c = ctx or default_context()
+    d = np.ascontiguousarray(np.asarray(desc, dtype=np.int64).reshape(-1, _abi.NMT_NS_DESC_WORDS))
+    n = int(d.shape[0])
+    dev = roots.device
+    for t in (namespaces, leaves, nodes, leaf_hashes, roots):
+        if t.dtype != torch.uint8 or t.device != dev or not t.is_contiguous():
+            raise ValueError("namespaces, leaves, nodes, leaf_hashes and roots must be contiguous uint8 tensors "
+                             "on one device")
+    n_leaves = leaves.numel() // leaf_len if leaf_len else int(d[:, 2].clip(min=0).sum())
+    n_proven = int(d[:, 2].clip(min=0, max=max(n_leaves, 0)).sum())
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    need = c._L.dagpu_nmt_verify_namespace_workspace_size(n, n_proven)
+    with torch.cuda.stream(s):
+        status = torch.empty((n,), dtype=torch.int32, device=dev)
+        if workspace is None:
+            workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+    if workspace.numel() < need:
+        raise ValueError("workspace smaller than dagpu_nmt_verify_namespace_workspace_size")
+    rc = c._L.dagpu_nmt_verify_namespace_batch_device(
+        c.handle, n, _abi.addr(d), _abi.addr(namespaces), namespaces.numel() // 29,
+        _abi.addr(leaves) if leaves.numel() else None, n_leaves, leaf_len,
+        _abi.addr(nodes) if nodes.numel() else None, nodes.numel() // ROOT,
+        _abi.addr(leaf_hashes) if leaf_hashes.numel() else None, leaf_hashes.numel() // ROOT,
+        _abi.addr(roots), roots.numel() // ROOT, _abi.addr(status), _abi.addr(workspace), _stream_handle(s))
+    if rc != 0:
+        raise DAError(rc, c.last_error())
+    return status
+
+
 class DeviceSquares:
     """n squares of width k resident on one GPU.
 

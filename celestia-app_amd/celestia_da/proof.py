@@ -10,6 +10,11 @@
   -> dagpu_merkle_verify / dagpu_nmt_verify_inclusion (host code of the library)
   many proofs at once (validate_batch, verify_inclusion_batch, merkle_verify_batch)
   -> dagpu_merkle_verify_batch / dagpu_nmt_verify_batch (hashed on the GPU)
+  nmt ProveNamespace / Proof.VerifyNamespace, absence proofs included
+  (celestia-node GetSharesByNamespace): NMTProof.verify_namespace,
+  verify_namespace_batch, prove_namespaces, verify_namespace_data
+  -> dagpu_nmt_verify_namespace(_batch), dagpu_nmt_prove_namespace_batch_device;
+  the rules are stated in include/dagpu.h (recalled from nmt v0.20.0, parity unpinned)
 
 The square is extended and hashed on the GPU, every row-tree node stays in HBM
 (dagpu_row_nodes_device) and the RFC-6962 tree over rowRoots||colRoots is
@@ -99,6 +104,30 @@ class NMTProof:
                                                    self.end, _abi.addr(nd), len(self.nodes), _abi.addr(rt))
         return rc == 0
 
+    def is_empty_proof(self) -> bool:
+        """nmt Proof.IsEmptyProof: start == end, no nodes, no leaf hash."""
+        return self.start == self.end and len(self.nodes) == 0 and len(self.leaf_hash) == 0
+
+    def is_of_absence(self) -> bool:
+        """nmt Proof.IsOfAbsence: the proof carries a leaf hash."""
+        return len(self.leaf_hash) > 0
+
+    def verify_namespace(self, nid: bytes, leaves: Sequence[bytes], root: bytes) -> bool:
+        """nmt Proof.VerifyNamespace (IgnoreMaxNamespace): `leaves` are the
+        tree's leaves WITH their 29-B namespace prefix (nid | share for a row
+        tree); each must start with nid.  True iff the leaves are every leaf of
+        nid under `root` (none for an absence or empty proof)."""
+        raw = _strip_prefix(self, nid, leaves, root)
+        if raw is None:
+            return False
+        ln = len(raw[0]) if raw else 0
+        nsb, lv, nd, rt = _bytes(nid), _bytes(b"".join(raw)), _bytes(b"".join(self.nodes)), _bytes(root)
+        lh = _bytes(self.leaf_hash)
+        rc = _abi.lib().dagpu_nmt_verify_namespace(_abi.addr(nsb), _abi.addr(lv), len(raw), ln, _i64(self.start),
+                                                   _i64(self.end), _abi.addr(nd), len(self.nodes),
+                                                   _abi.addr(lh) if self.leaf_hash else None, _abi.addr(rt))
+        return rc == 0
+
 
 @dataclass
 class RowProof:
@@ -163,6 +192,19 @@ class ShareProof:
 
 def _bytes(b: bytes) -> np.ndarray:
     return np.frombuffer(b, np.uint8) if len(b) else np.zeros(1, np.uint8)
+
+
+def _strip_prefix(p: "NMTProof", nid: bytes, leaves: Sequence[bytes], root: bytes) -> Optional[List[bytes]]:
+    """The shape checks of verify_namespace and nmt's leaf[:29] == nID check;
+    the leaves without their prefix, or None when a check fails."""
+    if len(nid) != 29 or len(root) != 90 or any(len(n) != 90 for n in p.nodes) or len(p.leaf_hash) not in (0, 90):
+        return None
+    if any(len(x) < 29 or bytes(x[:29]) != bytes(nid) for x in leaves):
+        return None
+    raw = [bytes(x[29:]) for x in leaves]
+    if any(len(x) != len(raw[0]) for x in raw):
+        return None
+    return raw
 
 
 # ---------------------------------------------------------------------------
@@ -299,6 +341,123 @@ def verify_inclusion_batch(items: Sequence[Tuple[NMTProof, bytes, Sequence[bytes
         for (pos, _), s in zip(group, st):
             out[pos] = int(s) == _abi.OK
     return out
+
+
+@dataclass
+class PackedNamespace(PackedNMT):
+    """PackedNMT with 9-word descriptors (word 8 = leaf_hash_index, -1 = none)
+    and the leaf-hash table of dagpu_nmt_verify_namespace_batch."""
+    leaf_hashes: bytes = b""
+    n_leaf_hashes: int = 0
+
+
+def pack_namespace_proofs(items: Sequence[Tuple[NMTProof, bytes, Sequence[bytes], bytes]],
+                          leaf_len: int) -> PackedNamespace:
+    """items: (proof, nid, leaves WITHOUT prefix, root), shapes already checked."""
+    nss, roots = {}, {}
+    desc = np.zeros((len(items), _abi.NMT_NS_DESC_WORDS), np.int64)
+    leaves, nodes, hashes = [], [], []
+    n_leaves = n_nodes = 0
+    for i, (p, ns, lv, root) in enumerate(items):
+        lh = -1
+        if p.leaf_hash:
+            lh = len(hashes)
+            hashes.append(bytes(p.leaf_hash))
+        desc[i] = (_i64(p.start), _i64(p.end), len(lv), n_leaves, len(p.nodes), n_nodes,
+                   _intern(nss, bytes(ns)), _intern(roots, bytes(root)), lh)
+        leaves.extend(bytes(x) for x in lv)
+        nodes.extend(bytes(x) for x in p.nodes)
+        n_leaves += len(lv)
+        n_nodes += len(p.nodes)
+    return PackedNamespace(desc, b"".join(nss), len(nss), b"".join(leaves), n_leaves, leaf_len, b"".join(nodes),
+                           n_nodes, b"".join(roots), len(roots), b"".join(hashes), len(hashes))
+
+
+def _run_namespace(pk: PackedNamespace, c: Context) -> np.ndarray:
+    status = np.full(len(pk.desc), _abi.ERR_ARG, np.int32)
+    desc = np.ascontiguousarray(pk.desc)
+    ns, lv, nd, rt, lh = (_bytes(pk.namespaces), _bytes(pk.leaves), _bytes(pk.nodes), _bytes(pk.roots),
+                          _bytes(pk.leaf_hashes))
+    c.check(c._L.dagpu_nmt_verify_namespace_batch(c.handle, len(desc), _abi.addr(desc), _abi.addr(ns), pk.n_ns,
+                                                  _abi.addr(lv), pk.n_leaves, pk.leaf_len, _abi.addr(nd),
+                                                  pk.n_nodes, _abi.addr(lh), pk.n_leaf_hashes, _abi.addr(rt),
+                                                  pk.n_roots, _abi.addr(status)))
+    return status
+
+
+def _verify_namespace_raw(entries, out: List[bool], ctx: Optional[Context]) -> List[bool]:
+    """entries: (position, leaf length, (proof, nid, leaves WITHOUT prefix, root))."""
+    if not entries:
+        return out
+    c = ctx or default_context()
+    for ln, group in _by_length(entries).items():
+        st = _run_namespace(pack_namespace_proofs([it for _, it in group], ln), c)
+        for (pos, _), s in zip(group, st):
+            out[pos] = int(s) == _abi.OK
+    return out
+
+
+def verify_namespace_batch(items: Sequence[Tuple[NMTProof, bytes, Sequence[bytes], bytes]],
+                           ctx: Optional[Context] = None) -> List[bool]:
+    """NMTProof.verify_namespace for every (proof, nid, leaves with prefix,
+    root) of `items`, hashed and folded on the GPU: one
+    dagpu_nmt_verify_namespace_batch call per distinct leaf length (proofs
+    without leaves go with length 0)."""
+    out = [False] * len(items)
+    entries = []
+    for i, (p, nid, lv, root) in enumerate(items):
+        raw = _strip_prefix(p, nid, lv, root)
+        if raw is not None:
+            entries.append((i, len(raw[0]) if raw else 0, (p, nid, raw, root)))
+    return _verify_namespace_raw(entries, out, ctx)
+
+
+def prove_namespaces(axis_nodes, namespaces: Sequence[bytes]) -> List[List[Tuple[int, NMTProof, List[bytes]]]]:
+    """nmt ProveNamespace of every namespace on every row tree of one resident
+    square (axis_nodes: inclusion.EDSAxisNodes): per namespace the list of
+    (row, proof, shares) for the rows whose root range contains it -- presence
+    proofs with their 512-B shares, absence proofs with none.  The other rows'
+    proof is the empty proof and is not listed.  One
+    dagpu_nmt_prove_namespace_batch_device call and one copy to the host."""
+    from .device import nmt_prove_namespace_batch_device
+    out: List[List[Tuple[int, NMTProof, List[bytes]]]] = [[] for _ in namespaces]
+    if not len(namespaces):
+        return out
+    nodes, _, shares, hashes, desc, pairs, _ = nmt_prove_namespace_batch_device(axis_nodes, namespaces)
+    nodes, shares, hashes = (t.cpu().numpy().tobytes() for t in (nodes, shares, hashes))
+    for d, (q, row) in zip(desc, pairs):
+        lh = hashes[90 * int(d[8]):90 * int(d[8]) + 90] if d[8] >= 0 else b""
+        p = NMTProof(int(d[0]), int(d[1]), [nodes[90 * j:90 * (j + 1)] for j in range(int(d[5]), int(d[5] + d[4]))], lh)
+        out[int(q)].append((int(row), p, [shares[512 * j:512 * (j + 1)] for j in range(int(d[3]), int(d[3] + d[2]))]))
+    return out
+
+
+def verify_namespace_data(row_roots: Sequence[bytes], nid: bytes,
+                          rows: Sequence[Tuple[int, NMTProof, Sequence[bytes]]],
+                          ctx: Optional[Context] = None) -> bool:
+    """The light client's whole check of a GetSharesByNamespace answer: `rows`
+    = (row, proof, shares) as prove_namespaces gives them (512-B shares, without
+    the prefix the tree prepends).  True iff every row root whose [min, max]
+    contains nid has exactly one entry and every entry verifies under its row
+    root by VerifyNamespace, all in one batched call."""
+    if len(nid) != 29 or any(len(r) != 90 for r in row_roots):
+        return False
+    seen = set()
+    entries = []
+    for i, (row, p, shares) in enumerate(rows):
+        if not 0 <= row < len(row_roots) or row in seen:
+            return False
+        seen.add(row)
+        if any(len(n) != 90 for n in p.nodes) or len(p.leaf_hash) not in (0, 90):
+            return False
+        ln = len(shares[0]) if shares else 0
+        if any(len(x) != ln for x in shares):
+            return False
+        entries.append((i, ln, (p, nid, [bytes(x) for x in shares], bytes(row_roots[row]))))
+    for row, root in enumerate(row_roots):
+        if bytes(root[:29]) <= bytes(nid) <= bytes(root[29:58]) and row not in seen:
+            return False
+    return all(_verify_namespace_raw(entries, [False] * len(entries), ctx))
 
 
 def merkle_verify_batch(items: Sequence[Tuple[MerkleProof, bytes, bytes]],

@@ -98,6 +98,21 @@ hipError_t launch_prove_emit(const ProveArgs& a, hipStream_t s);
 hipError_t launch_prove_namespaces(const ProveArgs& a, hipStream_t s);
 hipError_t launch_prove_shares(const ProveArgs& a, hipStream_t s);
 
+// Namespace search over the row trees of one square (nmt_namespace.hip;
+// arithmetic in ns_find.hpp).  One lane per (query, row).
+struct NsFindArgs {
+  long n_q;                  // queries
+  int w;                     // leaves per row tree (2k)
+  const uint8_t* queries;    // n_q namespaces, zero padded to 32 B, 16-B aligned
+  const uint8_t* row_nodes;  // dagpu_row_nodes_device store (96-B records)
+  int32_t* ranges;           // n_q x w x {kind, start, end}
+};
+hipError_t launch_ns_find(const NsFindArgs& a, hipStream_t s);
+// Level-0 records rec_index[0 .. n) of the row store as packed 90-B nodes: the
+// leaf hashes of absence proofs.
+hipError_t launch_ns_leaf_nodes(const uint8_t* row_nodes, const int64_t* rec_index, long n, uint8_t* out,
+                                hipStream_t s);
+
 // Host-side level plan of one forest.  Leaves (level 0) are either packed tree
 // after tree (ragged: counts[t] leaves each) or uniform with (tstride,
 // lstride) addressing inside a caller-owned leaf array.  Levels >= 1 are packed

@@ -4,7 +4,12 @@
 //   ShareProof.VerifyProof) for many proofs: a leaf pass (one lane per proven
 //   leaf) and a fold pass (one lane per proof);
 //   crypto/merkle Proof.Verify (celestia-core RowProof.Validate) for many
-//   proofs: one lane per proof.
+//   proofs: one lane per proof;
+//   nmt Proof.VerifyNamespace (presence, absence and empty proofs; rules of
+//   include/dagpu.h, specification dagpu_nmt_verify_namespace): the same two
+//   passes instantiated with NS = true -- 9-word descriptors, an absence
+//   proof's one leaf record copied from its leaf hash, the empty-form decision
+//   against the root, and the completeness test where a proof node is popped.
 //
 // The specification is the library's own host verifiers
 // (dagpu_nmt_verify_inclusion / dagpu_merkle_verify, trees.cpp): the fold walks
@@ -194,11 +199,21 @@ __device__ __forceinline__ void pv_rfc_inner(const uint32_t (&l)[8], const uint3
 // Leaf pass: one lane per proven leaf; record ns | ns | SHA256(0x00 | ns | leaf)
 // with ns the namespace the proof claims.
 // ---------------------------------------------------------------------------
+template <bool NS>
 __global__ __launch_bounds__(256) void pv_nmt_leaf_kernel(PvNmtArgs a, long n_records) {
   const long g = (long)blockIdx.x * 256 + threadIdx.x;
   if (g >= n_records) return;
   const long i = pv_find(a.rec_off, a.n, g);
-  const int64_t* d = a.desc + i * kPvDescNmt;
+  const int64_t* d = a.desc + i * (NS ? kPvDescNmtNs : kPvDescNmt);
+  if constexpr (NS) {
+    if (d[8] >= 0) {  // absence: the one record is the proof's leaf hash, nothing is hashed
+      uint32_t mn[8], mx[8], dg[8];
+      load_node90(a.leaf_hashes + d[8] * kNodeSize, mn, mx, dg);
+      uint8_t* o = a.recs + g * kRecNmt;
+      store_q(o, mn); store_q(o + 32, mx); store_q(o + 64, dg);
+      return;
+    }
+  }
   const long leaf = d[3] + (g - a.rec_off[i]);
   const uint8_t* nsp = a.ns + d[6] * kNsSize;
   const uint8_t* src = a.leaves + leaf * a.leaf_len;
@@ -229,6 +244,19 @@ __global__ __launch_bounds__(256) void pv_nmt_leaf_kernel(PvNmtArgs a, long n_re
 // ---------------------------------------------------------------------------
 enum { kPvEval = 0, kPvAscend = 1, kPvHash = 2, kPvTail = 3 };
 
+// NS: Proof.VerifyNamespace.  A proof node popped for a subtree left of the range
+// must have max < nid, one popped right of it (the tail included) nid < min; nid
+// is re-read from the namespace table at each pop rather than kept live.
+template <bool NS>
+__device__ __forceinline__ bool pv_incomplete(const uint8_t* nsp, bool left, const uint32_t (&mn)[8],
+                                              const uint32_t (&mx)[8]) {
+  if constexpr (!NS) return false;
+  uint32_t nid[8];
+  load_ns29(nsp, nid);
+  return left ? !ns_less(mx, nid) : !ns_less(nid, mn);
+}
+
+template <bool NS>
 __global__ __launch_bounds__(kPvFoldLanes) void pv_nmt_fold_kernel(PvNmtArgs a) {
   __shared__ int32_t s_ref[kPvMaxHeight + 2][kPvFoldLanes];  // [height][lane]: node index or -1
   const int lane = threadIdx.x;
@@ -237,14 +265,37 @@ __global__ __launch_bounds__(kPvFoldLanes) void pv_nmt_fold_kernel(PvNmtArgs a) 
   int32_t result = DAGPU_ERR_PROOF;
   int64_t start = 0, end = 1, nl = 0, nn = 0, node_off = 0, rec0 = 0, cs0 = 0, root_ix = 0;
   int depth = 0;
+  const uint8_t* nsp = a.ns;
   if (!done) {
-    const int64_t* d = a.desc + i * kPvDescNmt;
+    const int64_t* d = a.desc + i * (NS ? kPvDescNmtNs : kPvDescNmt);
     start = d[0]; end = d[1]; nl = d[2]; nn = d[4]; node_off = d[5]; root_ix = d[7];
     rec0 = a.rec_off[i];
     cs0 = a.cs_off[i];
     depth = (int)(a.cs_off[i + 1] - cs0);
     // a range the host verifier rejects has no records: DAGPU_ERR_PROOF
-    if (depth == 0) { done = true; end = 1; }
+    if (depth == 0) done = true;
+    if constexpr (NS) {
+      nsp = a.ns + d[6] * kNsSize;
+      const int64_t lh = d[8];
+      if (start == end && nn == 0 && lh < 0) {
+        // the empty form: valid without leaves when nid is outside the root's range
+        if (nl == 0) {
+          uint32_t nid[8], rmn[8], rmx[8], rdg[8];
+          load_ns29(nsp, nid);
+          load_node90(a.roots + root_ix * kNodeSize, rmn, rmx, rdg);
+          if (ns_less(nid, rmn) || ns_less(rmx, nid)) result = DAGPU_OK;
+        }
+        done = true;
+      } else if (!done && lh >= 0) {
+        // absence: nid < leafHash.min, read back from the proof's one leaf record
+        uint32_t nid[8], hmn[8];
+        load_ns29(nsp, nid);
+        load_q(a.recs + rec0 * kRecNmt, hmn);
+        if (!ns_less(nid, hmn)) done = true;
+        nl = 1;  // the record stands for the one leaf of the fold
+      }
+    }
+    if (done) end = 1;
   }
   int H = 0;
   while (H < kPvMaxHeight && ((int64_t)1 << H) < end) H++;
@@ -285,6 +336,7 @@ __global__ __launch_bounds__(kPvFoldLanes) void pv_nmt_fold_kernel(PvNmtArgs a) 
               ref = (int32_t)next_node;
               next_node++;
               okv = true;
+              if (pv_incomplete<NS>(nsp, hi <= start, vmn, vmx)) done = true;
             }
             phase = kPvAscend;
           } else {
@@ -340,6 +392,7 @@ __global__ __launch_bounds__(kPvFoldLanes) void pv_nmt_fold_kernel(PvNmtArgs a) 
             load_node90(a.nodes + (node_off + next_node) * kNodeSize, vmn, vmx, vdg);
             next_node++;
             phase = kPvHash;
+            if (pv_incomplete<NS>(nsp, false, vmn, vmx)) done = true;
           } else {
             uint32_t rmn[8], rmx[8], rdg[8];
             load_node90(a.roots + root_ix * kNodeSize, rmn, rmx, rdg);
@@ -448,14 +501,21 @@ __global__ __launch_bounds__(256) void pv_merkle_kernel(PvMerkleArgs a) {
 
 hipError_t launch_pv_nmt_leaves(const PvNmtArgs& a, long n_records, hipStream_t s) {
   if (n_records <= 0) return hipSuccess;
-  hipLaunchKernelGGL(pv_nmt_leaf_kernel, dim3((unsigned)((n_records + 255) / 256)), dim3(256), 0, s, a, n_records);
+  const dim3 grid((unsigned)((n_records + 255) / 256));
+  if (a.namespace_rules)
+    hipLaunchKernelGGL(pv_nmt_leaf_kernel<true>, grid, dim3(256), 0, s, a, n_records);
+  else
+    hipLaunchKernelGGL(pv_nmt_leaf_kernel<false>, grid, dim3(256), 0, s, a, n_records);
   return hipGetLastError();
 }
 
 hipError_t launch_pv_nmt_fold(const PvNmtArgs& a, hipStream_t s) {
   if (a.n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(pv_nmt_fold_kernel, dim3((unsigned)((a.n + kPvFoldLanes - 1) / kPvFoldLanes)),
-                     dim3(kPvFoldLanes), 0, s, a);
+  const dim3 grid((unsigned)((a.n + kPvFoldLanes - 1) / kPvFoldLanes));
+  if (a.namespace_rules)
+    hipLaunchKernelGGL(pv_nmt_fold_kernel<true>, grid, dim3(kPvFoldLanes), 0, s, a);
+  else
+    hipLaunchKernelGGL(pv_nmt_fold_kernel<false>, grid, dim3(kPvFoldLanes), 0, s, a);
   return hipGetLastError();
 }
 

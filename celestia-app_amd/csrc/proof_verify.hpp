@@ -9,6 +9,7 @@
 namespace dagpu {
 
 constexpr int kPvDescNmt = 8;     // int64 per nmt descriptor (dagpu.h DAGPU_NMT_DESC_*)
+constexpr int kPvDescNmtNs = 9;   // namespace proofs: the eight above + leaf_hash_index (DAGPU_NMT_NS_DESC_WORDS)
 constexpr int kPvDescMerkle = 6;  // int64 per merkle descriptor
 constexpr int kPvMaxHeight = 62;  // est = 2^H >= end, end <= 2^62
 constexpr int kPvFoldLanes = 64;  // proofs per fold block (one wave)
@@ -25,7 +26,8 @@ inline int pv_stack_depth(int64_t nl) {
 
 struct PvNmtArgs {
   long n;                  // proofs
-  const int64_t* desc;     // n x kPvDescNmt, validated
+  int namespace_rules;     // 0: VerifyInclusion; 1: VerifyNamespace (kPvDescNmtNs words, leaf_hashes)
+  const int64_t* desc;     // n x kPvDescNmt (or kPvDescNmtNs), validated
   const int64_t* rec_off;  // n + 1: first leaf record of proof i (prefix sums)
   const int64_t* cs_off;   // n: first stack record of proof i; < 0 = range rejected
   const uint8_t* ns;       // namespace table, 29 B each
@@ -34,6 +36,7 @@ struct PvNmtArgs {
   int fast512;             // leaf_len == 512 and `leaves` 16-B aligned
   const uint8_t* nodes;    // packed 90-B nodes
   const uint8_t* roots;    // packed 90-B roots
+  const uint8_t* leaf_hashes;  // packed 90-B leaf hashes of absence proofs (namespace_rules)
   uint8_t* recs;           // rec_off[n] leaf records (96 B)
   uint8_t* cstack;         // stack records (96 B)
   int32_t* status;

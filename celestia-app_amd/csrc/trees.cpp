@@ -19,6 +19,16 @@
 //                          trees of a resident square (pkg/proof/proof.go:87-150),
 //                          nodes selected on the device (nmt_prove.hip); request
 //                          checks and layout in prove_layout.hpp
+//   dagpu_nmt_verify_namespace / dagpu_nmt_verify_namespace_batch(_device)
+//                          nmt Proof.VerifyNamespace: presence with completeness,
+//                          absence and empty proofs (rules stated in dagpu.h,
+//                          recalled from nmt v0.20.0); the fold is shared with
+//                          VerifyInclusion (nmt_fold_verify)
+//   dagpu_nmt_namespace_ranges_device / dagpu_nmt_prove_namespace_batch_device
+//                          nmt ProveNamespace on every row tree of a resident
+//                          square for a list of namespaces: search on the device
+//                          (nmt_namespace.hip, ns_find.hpp), then the range-proof
+//                          emit and gather kernels
 // Each call uploads the pushes once, hashes every leaf and level of every
 // tree in a handful of launches (nmt_forest.hip) and returns the roots.
 #include <hip/hip_runtime.h>
@@ -34,6 +44,7 @@
 #include "forest.hpp"
 #include "kernels.hpp"
 #include "host_sha256.hpp"
+#include "ns_find.hpp"
 #include "proof_verify.hpp"
 #include "prove_layout.hpp"
 #include "runtime.hpp"
@@ -139,6 +150,63 @@ std::vector<long> mmr_sizes(uint64_t total, uint64_t max_tree) {
   return out;
 }
 
+// The fold of nmt Proof.VerifyInclusion and Proof.VerifyNamespace over n leaf
+// nodes (90 B each) proven at [start, end), start < end.  With `nid` the
+// completeness rule of VerifyNamespace holds too: a proof node consumed left of
+// the range must have max < nid, one consumed right of it (the leftover nodes
+// folded on the right included) nid < min.
+int nmt_fold_verify(const uint8_t* lh, size_t n, int64_t start, int64_t end, const uint8_t* nodes, size_t nnodes,
+                    const uint8_t* root90, const uint8_t* nid) {
+  using namespace dagpu::host;
+  size_t next_leaf = 0, next_node = 0;
+  bool ok = true;
+  auto complete = [&](const uint8_t* node, bool left) {
+    if (!nid) return;
+    if (left ? !(memcmp(node + kNs, nid, kNs) < 0) : !(memcmp(nid, node, kNs) < 0)) ok = false;
+  };
+  // nmt getSplitPoint: largest power of two strictly below length (length >= 2)
+  auto split = [](int64_t len) {
+    int64_t k = 1;
+    while (k * 2 < len) k *= 2;
+    return k;
+  };
+  // verifyLeafHashes.computeRoot: proof nodes fill the subtrees disjoint from
+  // [start, end), popped left to right; an absent right subtree is skipped.
+  std::function<bool(int64_t, int64_t, uint8_t*)> root_of = [&](int64_t lo, int64_t hi, uint8_t* out) -> bool {
+    if (hi - lo == 1 && start <= lo && lo < end) {
+      memcpy(out, &lh[next_leaf++ * kNodeLen], kNodeLen);
+      return true;
+    }
+    if (hi - lo == 1 || hi <= start || lo >= end) {
+      if (next_node >= nnodes) return false;
+      complete(nodes + next_node * kNodeLen, hi <= start);
+      memcpy(out, nodes + next_node++ * kNodeLen, kNodeLen);
+      return true;
+    }
+    const int64_t k = split(hi - lo);
+    uint8_t l[kNodeLen], r[kNodeLen];
+    if (!root_of(lo, lo + k, l)) return false;  // a missing left subtree cannot verify
+    if (!root_of(lo + k, hi, r)) {
+      memcpy(out, l, kNodeLen);
+      return true;
+    }
+    if (!nmt_hash_node(l, r, out)) ok = false;
+    return true;
+  };
+  int64_t est = 1;
+  while (est < end) est *= 2;  // getSplitPoint(end) * 2: the subtree holding the range
+  uint8_t root[kNodeLen];
+  if (!root_of(0, est, root)) return DAGPU_ERR_PROOF;
+  for (; next_node < nnodes; next_node++) {  // remaining right-hand nodes
+    uint8_t t[kNodeLen];
+    complete(nodes + next_node * kNodeLen, false);
+    if (!nmt_hash_node(root, nodes + next_node * kNodeLen, t)) ok = false;
+    memcpy(root, t, kNodeLen);
+  }
+  if (!ok || next_leaf != n) return DAGPU_ERR_PROOF;
+  return memcmp(root, root90, kNodeLen) == 0 ? DAGPU_OK : DAGPU_ERR_PROOF;
+}
+
 // ---- batched proof verification (proof_verify.hip) ----
 
 size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
@@ -156,30 +224,47 @@ bool pv_range_rejected(const int64_t* d) {
   return start < 0 || start >= end || end > ((int64_t)1 << kPvMaxHeight) || nl != end - start;
 }
 
+// Leaf records of a 9-word namespace descriptor (dagpu_nmt_verify_namespace):
+// 0 when the host verifier rejects it before it hashes, and for the empty form,
+// which the fold kernel decides against the root; 1 for an absence proof (its
+// leaf hash; nid < leafHash.min is tested on the device, where the tables
+// are); n_leaves for a presence proof.
+int64_t pv_ns_records(const int64_t* d) {
+  const int64_t start = d[0], end = d[1], nl = d[2], nn = d[4], lh = d[8];
+  if (start == end && nn == 0 && lh < 0) return 0;
+  if (start < 0 || start >= end || end > ((int64_t)1 << kPvMaxHeight)) return 0;
+  if (lh >= 0) return nl == 0 && end - start == 1 ? 1 : 0;
+  return nl == end - start ? nl : 0;
+}
+
 // Host image of what the nmt kernels read besides the bulk data.
 struct PvNmtPlan {
-  std::vector<int64_t> meta;  // desc (8 n) | rec_off (n + 1) | cs_off (n + 1)
+  std::vector<int64_t> meta;  // desc (8 n, or 9 n) | rec_off (n + 1) | cs_off (n + 1)
   long n_records = 0, n_stack = 0;
 };
 
 // Every descriptor against the totals; nothing is launched when one fails.
+// words = kPvDescNmt, or kPvDescNmtNs with the leaf-hash table of n_lh entries.
 int pv_check_nmt(dagpu_ctx* ctx, size_t n, const int64_t* desc, size_t n_ns, size_t n_leaves, size_t n_nodes,
-                 size_t n_roots, PvNmtPlan* plan) {
-  plan->meta.resize(n * kPvDescNmt + 2 * (n + 1));
-  int64_t* rec_off = plan->meta.data() + n * kPvDescNmt;
+                 size_t n_roots, PvNmtPlan* plan, int words = kPvDescNmt, size_t n_lh = 0) {
+  const bool ns_rules = words == kPvDescNmtNs;
+  plan->meta.resize(n * words + 2 * (n + 1));
+  int64_t* rec_off = plan->meta.data() + n * words;
   int64_t* cs_off = rec_off + (n + 1);
   long recs = 0, stack = 0;
   for (size_t i = 0; i < n; i++) {
-    const int64_t* d = desc + i * kPvDescNmt;
+    const int64_t* d = desc + i * words;
     if (!pv_span_ok(d[3], d[2], n_leaves) || !pv_span_ok(d[5], d[4], n_nodes) || d[4] > INT32_MAX ||
-        d[6] < 0 || (uint64_t)d[6] >= n_ns || d[7] < 0 || (uint64_t)d[7] >= n_roots)
+        d[6] < 0 || (uint64_t)d[6] >= n_ns || d[7] < 0 || (uint64_t)d[7] >= n_roots ||
+        (ns_rules && (d[8] < -1 || (d[8] >= 0 && (uint64_t)d[8] >= n_lh))))
       return set_err(ctx, DAGPU_ERR_ARG, "proof descriptor " + std::to_string(i) + " points outside the buffers");
-    memcpy(plan->meta.data() + i * kPvDescNmt, d, kPvDescNmt * sizeof(int64_t));
+    memcpy(plan->meta.data() + i * words, d, words * sizeof(int64_t));
     rec_off[i] = recs;
     cs_off[i] = stack;
-    if (!pv_range_rejected(d)) {
-      recs += (long)d[2];
-      stack += pv_stack_depth(d[2]);
+    const int64_t nrec = ns_rules ? pv_ns_records(d) : pv_range_rejected(d) ? 0 : d[2];
+    if (nrec > 0) {
+      recs += (long)nrec;
+      stack += pv_stack_depth(nrec);
     }
   }
   rec_off[n] = recs;
@@ -189,19 +274,22 @@ int pv_check_nmt(dagpu_ctx* ctx, size_t n, const int64_t* desc, size_t n_ns, siz
   return DAGPU_OK;
 }
 
-size_t pv_nmt_meta_bytes(size_t n) { return align256((n * kPvDescNmt + 2 * (n + 1)) * sizeof(int64_t)); }
+size_t pv_nmt_meta_bytes(size_t n, int words = kPvDescNmt) {
+  return align256((n * words + 2 * (n + 1)) * sizeof(int64_t));
+}
 
 // Upload the plan and enqueue the leaf and fold passes.  Returns once the
 // upload is complete (the plan and the caller's descriptors may go).
 int pv_nmt_enqueue(dagpu_ctx* ctx, size_t n, const PvNmtPlan& plan, const uint8_t* d_ns, const uint8_t* d_leaves,
                    size_t leaf_len, const uint8_t* d_nodes, const uint8_t* d_roots, int32_t* d_status,
-                   uint8_t* d_ws, hipStream_t s) {
+                   uint8_t* d_ws, hipStream_t s, int words = kPvDescNmt, const uint8_t* d_leaf_hashes = nullptr) {
   HIP_TRY(ctx, hipMemcpyAsync(d_ws, plan.meta.data(), plan.meta.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
   HIP_TRY(ctx, hipStreamSynchronize(s));
   PvNmtArgs a{};
   a.n = (long)n;
+  a.namespace_rules = words == kPvDescNmtNs;
   a.desc = (const int64_t*)d_ws;
-  a.rec_off = a.desc + n * kPvDescNmt;
+  a.rec_off = a.desc + n * words;
   a.cs_off = a.rec_off + (n + 1);
   a.ns = d_ns;
   a.leaves = d_leaves;
@@ -209,7 +297,8 @@ int pv_nmt_enqueue(dagpu_ctx* ctx, size_t n, const PvNmtPlan& plan, const uint8_
   a.fast512 = leaf_len == (size_t)kShareSize && (((uintptr_t)d_leaves) & 15) == 0;
   a.nodes = d_nodes;
   a.roots = d_roots;
-  a.recs = d_ws + pv_nmt_meta_bytes(n);
+  a.leaf_hashes = d_leaf_hashes;
+  a.recs = d_ws + pv_nmt_meta_bytes(n, words);
   a.cstack = a.recs + (size_t)plan.n_records * kRecNmt;
   a.status = d_status;
   HIP_TRY(ctx, launch_pv_nmt_leaves(a, plan.n_records, s));
@@ -513,47 +602,30 @@ int dagpu_nmt_verify_inclusion(const uint8_t* ns29, const uint8_t* leaves, size_
   if (start < 0 || start >= end || (int64_t)n != end - start) return DAGPU_ERR_PROOF;
   std::vector<uint8_t> lh(n * kNodeLen);
   for (size_t i = 0; i < n; i++) nmt_hash_leaf(ns29, leaves + i * leaf_len, leaf_len, &lh[i * kNodeLen]);
-  size_t next_leaf = 0, next_node = 0;
-  bool ok = true;
-  // nmt getSplitPoint: largest power of two strictly below length (length >= 2)
-  auto split = [](int64_t len) {
-    int64_t k = 1;
-    while (k * 2 < len) k *= 2;
-    return k;
-  };
-  // verifyLeafHashes.computeRoot: proof nodes fill the subtrees disjoint from
-  // [start, end), popped left to right; an absent right subtree is skipped.
-  std::function<bool(int64_t, int64_t, uint8_t*)> root_of = [&](int64_t lo, int64_t hi, uint8_t* out) -> bool {
-    if (hi - lo == 1 && start <= lo && lo < end) {
-      memcpy(out, &lh[next_leaf++ * kNodeLen], kNodeLen);
-      return true;
-    }
-    if (hi - lo == 1 || hi <= start || lo >= end) {
-      if (next_node >= nnodes) return false;
-      memcpy(out, nodes + next_node++ * kNodeLen, kNodeLen);
-      return true;
-    }
-    const int64_t k = split(hi - lo);
-    uint8_t l[kNodeLen], r[kNodeLen];
-    if (!root_of(lo, lo + k, l)) return false;  // a missing left subtree cannot verify
-    if (!root_of(lo + k, hi, r)) {
-      memcpy(out, l, kNodeLen);
-      return true;
-    }
-    if (!nmt_hash_node(l, r, out)) ok = false;
-    return true;
-  };
-  int64_t est = 1;
-  while (est < end) est *= 2;  // getSplitPoint(end) * 2: the subtree holding the range
-  uint8_t root[kNodeLen];
-  if (!root_of(0, est, root)) return DAGPU_ERR_PROOF;
-  for (; next_node < nnodes; next_node++) {  // remaining right-hand nodes
-    uint8_t t[kNodeLen];
-    if (!nmt_hash_node(root, nodes + next_node * kNodeLen, t)) ok = false;
-    memcpy(root, t, kNodeLen);
+  return nmt_fold_verify(lh.data(), n, start, end, nodes, nnodes, root90, nullptr);
+}
+
+int dagpu_nmt_verify_namespace(const uint8_t* ns29, const uint8_t* leaves, size_t n, size_t leaf_len,
+                               int64_t start, int64_t end, const uint8_t* nodes, size_t nnodes,
+                               const uint8_t* leaf_hash90, const uint8_t* root90) {
+  using namespace dagpu::host;
+  if (!ns29 || !root90 || (n && !leaves) || (nnodes && !nodes)) return DAGPU_ERR_ARG;
+  // the empty form: nid is outside the root's namespace range and nothing is shipped
+  if (start == end && nnodes == 0 && !leaf_hash90) {
+    if (n != 0) return DAGPU_ERR_PROOF;
+    const bool outside = memcmp(ns29, root90, kNs) < 0 || memcmp(root90 + kNs, ns29, kNs) < 0;
+    return outside ? DAGPU_OK : DAGPU_ERR_PROOF;
   }
-  if (!ok || next_leaf != n) return DAGPU_ERR_PROOF;
-  return memcmp(root, root90, kNodeLen) == 0 ? DAGPU_OK : DAGPU_ERR_PROOF;
+  if (start < 0 || start >= end || end > ((int64_t)1 << kPvMaxHeight)) return DAGPU_ERR_PROOF;
+  if (leaf_hash90) {
+    // absence: the leaf node of the first leaf with a larger namespace, no leaf data
+    if (n != 0 || end - start != 1 || !(memcmp(ns29, leaf_hash90, kNs) < 0)) return DAGPU_ERR_PROOF;
+    return nmt_fold_verify(leaf_hash90, 1, start, end, nodes, nnodes, root90, ns29);
+  }
+  if ((int64_t)n != end - start) return DAGPU_ERR_PROOF;
+  std::vector<uint8_t> lh(n * kNodeLen);
+  for (size_t i = 0; i < n; i++) nmt_hash_leaf(ns29, leaves + i * leaf_len, leaf_len, &lh[i * kNodeLen]);
+  return nmt_fold_verify(lh.data(), n, start, end, nodes, nnodes, root90, ns29);
 }
 
 int dagpu_merkle_verify(const uint8_t* root32, const uint8_t* leaf, size_t leaf_len, int64_t index,
@@ -649,6 +721,249 @@ int dagpu_nmt_verify_batch(dagpu_ctx* ctx, size_t n, const int64_t* desc, const 
   HIP_TRY(ctx, hipMemcpyAsync(st.data(), d + o_st, 4 * n, hipMemcpyDeviceToHost, s));
   HIP_TRY(ctx, hipStreamSynchronize(s));
   memcpy(status, st.data(), 4 * n);
+  return DAGPU_OK;
+}
+
+size_t dagpu_nmt_verify_namespace_workspace_size(size_t n, size_t n_leaves) {
+  // as dagpu_nmt_verify_workspace_size with 9-word descriptors; an absence
+  // proof has one record and no leaf, so every proof may add one
+  return pv_nmt_meta_bytes(n, kPvDescNmtNs) + (size_t)kRecNmt * (2 * (n_leaves + n) + 3 * n) + 256;
+}
+
+int dagpu_nmt_verify_namespace_batch_device(dagpu_ctx* ctx, size_t n, const int64_t* desc,
+                                            const uint8_t* d_namespaces, size_t n_ns, const uint8_t* d_leaves,
+                                            size_t n_leaves, size_t leaf_len, const uint8_t* d_nodes, size_t n_nodes,
+                                            const uint8_t* d_leaf_hashes, size_t n_leaf_hashes,
+                                            const uint8_t* d_roots, size_t n_roots, int32_t* d_status,
+                                            void* d_workspace, void* stream) {
+  if (!ctx) return DAGPU_ERR_ARG;
+  if (n == 0) return DAGPU_OK;
+  if (!desc || !d_status || !d_workspace || (((uintptr_t)d_workspace) & 15) != 0 || (n_ns && !d_namespaces) ||
+      (n_leaves && leaf_len && !d_leaves) || (n_nodes && !d_nodes) || (n_leaf_hashes && !d_leaf_hashes) ||
+      (n_roots && !d_roots))
+    return set_err(ctx, DAGPU_ERR_ARG, "dagpu_nmt_verify_namespace_batch_device: null or misaligned buffer");
+  PvNmtPlan plan;
+  int rc = pv_check_nmt(ctx, n, desc, n_ns, n_leaves, n_nodes, n_roots, &plan, kPvDescNmtNs, n_leaf_hashes);
+  if (rc) return rc;
+  return pv_nmt_enqueue(ctx, n, plan, d_namespaces, d_leaves, leaf_len, d_nodes, d_roots, d_status,
+                        (uint8_t*)d_workspace, (hipStream_t)stream, kPvDescNmtNs, d_leaf_hashes);
+}
+
+int dagpu_nmt_verify_namespace_batch(dagpu_ctx* ctx, size_t n, const int64_t* desc, const uint8_t* namespaces,
+                                     size_t n_ns, const uint8_t* leaves, size_t n_leaves, size_t leaf_len,
+                                     const uint8_t* nodes, size_t n_nodes, const uint8_t* leaf_hashes,
+                                     size_t n_leaf_hashes, const uint8_t* roots, size_t n_roots, int32_t* status) {
+  if (!ctx) return DAGPU_ERR_ARG;
+  if (n == 0) return DAGPU_OK;
+  if (!desc || !status || (n_ns && !namespaces) || (n_leaves && leaf_len && !leaves) || (n_nodes && !nodes) ||
+      (n_leaf_hashes && !leaf_hashes) || (n_roots && !roots))
+    return set_err(ctx, DAGPU_ERR_ARG, "dagpu_nmt_verify_namespace_batch: null buffer");
+  PvNmtPlan plan;
+  int rc = pv_check_nmt(ctx, n, desc, n_ns, n_leaves, n_nodes, n_roots, &plan, kPvDescNmtNs, n_leaf_hashes);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> g(ctx->mu);
+  (void)hipSetDevice(ctx->device);
+  hipStream_t s = ctx->stream;
+  const size_t b_ns = n_ns * kNsSize, b_lv = n_leaves * leaf_len, b_nd = n_nodes * kNodeSize,
+               b_lh = n_leaf_hashes * kNodeSize, b_rt = n_roots * kNodeSize;
+  const size_t o_ns = 0, o_lv = o_ns + align256(b_ns), o_nd = o_lv + align256(b_lv), o_lh = o_nd + align256(b_nd),
+               o_rt = o_lh + align256(b_lh), o_st = o_rt + align256(b_rt), o_ws = o_st + align256(4 * n);
+  const size_t ws = pv_nmt_meta_bytes(n, kPvDescNmtNs) + (size_t)kRecNmt * (size_t)(plan.n_records + plan.n_stack) + 256;
+  PvScratch m;
+  HIP_TRY(ctx, hipMalloc(&m.p, o_ws + ws));
+  uint8_t* d = (uint8_t*)m.p;
+  if (b_ns) HIP_TRY(ctx, hipMemcpyAsync(d + o_ns, namespaces, b_ns, hipMemcpyHostToDevice, s));
+  if (b_lv) HIP_TRY(ctx, hipMemcpyAsync(d + o_lv, leaves, b_lv, hipMemcpyHostToDevice, s));
+  if (b_nd) HIP_TRY(ctx, hipMemcpyAsync(d + o_nd, nodes, b_nd, hipMemcpyHostToDevice, s));
+  if (b_lh) HIP_TRY(ctx, hipMemcpyAsync(d + o_lh, leaf_hashes, b_lh, hipMemcpyHostToDevice, s));
+  if (b_rt) HIP_TRY(ctx, hipMemcpyAsync(d + o_rt, roots, b_rt, hipMemcpyHostToDevice, s));
+  rc = pv_nmt_enqueue(ctx, n, plan, d + o_ns, d + o_lv, leaf_len, d + o_nd, d + o_rt, (int32_t*)(d + o_st),
+                      d + o_ws, s, kPvDescNmtNs, d + o_lh);
+  if (rc) {
+    (void)hipStreamSynchronize(s);
+    return rc;
+  }
+  std::vector<int32_t> st(n);
+  HIP_TRY(ctx, hipMemcpyAsync(st.data(), d + o_st, 4 * n, hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+  memcpy(status, st.data(), 4 * n);
+  return DAGPU_OK;
+}
+
+// ---- namespace search and proofs from a resident square (nmt_namespace.hip) ----
+
+size_t dagpu_nmt_namespace_workspace_size(uint32_t k, size_t n_q) {
+  if (k == 0 || !is_pow2(k) || k > (uint32_t)kMaxK) return 0;
+  const size_t w = 2 * (size_t)k, pairs = n_q * w;
+  // padded queries | ranges of every (query, row) | then, for the proof call:
+  // packed requests, node and leaf offsets and absence records of <= pairs proofs
+  return align256(32 * n_q) + align256(pairs * kNsRangeWords * sizeof(int32_t)) +
+         align256((4 * pairs + 2) * sizeof(int64_t)) + 256;
+}
+
+namespace {
+
+// Search every (query, row) on the device and read the ranges back: one
+// synchronisation.  `ranges` gets n_q * 2k triples; counts as dagpu.h states.
+int ns_search(dagpu_ctx* ctx, uint32_t k, size_t n_q, const uint8_t* namespaces, const uint8_t* d_row_nodes,
+              int32_t* ranges, int64_t counts[4], uint8_t* d_ws, hipStream_t s) {
+  const size_t w = 2 * (size_t)k, pairs = n_q * w;
+  const int m = prove_log2((uint32_t)w);
+  std::vector<uint8_t> padded(32 * n_q, 0);
+  for (size_t q = 0; q < n_q; q++) memcpy(&padded[32 * q], namespaces + q * kNsSize, kNsSize);
+  int32_t* d_ranges = (int32_t*)(d_ws + align256(32 * n_q));
+  HIP_TRY(ctx, hipMemcpyAsync(d_ws, padded.data(), padded.size(), hipMemcpyHostToDevice, s));
+  NsFindArgs a{};
+  a.n_q = (long)n_q;
+  a.w = (int)w;
+  a.queries = d_ws;
+  a.row_nodes = d_row_nodes;
+  a.ranges = d_ranges;
+  hipError_t e = launch_ns_find(a, s);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(ranges, d_ranges, pairs * kNsRangeWords * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+  const hipError_t e2 = hipStreamSynchronize(s);  // `padded` is read by the upload: always wait
+  HIP_TRY(ctx, e);
+  HIP_TRY(ctx, e2);
+  counts[0] = counts[1] = counts[2] = counts[3] = 0;
+  for (size_t p = 0; p < pairs; p++) {
+    const int32_t* r = ranges + p * kNsRangeWords;
+    // what the kernel wrote is re-checked before anything is laid out from it
+    if (r[0] < kNsOutside || r[0] > kNsAbsent || (r[0] != kNsOutside && !(0 <= r[1] && r[1] < r[2] && r[2] <= (int32_t)w)))
+      return set_err(ctx, DAGPU_ERR_DEVICE, "namespace search returned a range outside the row");
+    if (r[0] == kNsOutside) continue;
+    counts[0]++;
+    counts[2] += prove_node_count(m, (uint32_t)r[1], (uint32_t)r[2]);
+    if (r[0] == kNsAbsent) counts[1]++; else counts[3] += r[2] - r[1];
+  }
+  return DAGPU_OK;
+}
+
+int ns_common_check(dagpu_ctx* ctx, const char* who, const void* namespaces, const void* d_row_nodes,
+                    const void* d_workspace) {
+  if (!namespaces || !d_row_nodes || !d_workspace)
+    return set_err(ctx, DAGPU_ERR_ARG, std::string(who) + ": null buffer");
+  if ((((uintptr_t)d_workspace | (uintptr_t)d_row_nodes) & 15) != 0)
+    return set_err(ctx, DAGPU_ERR_ARG, std::string(who) + ": misaligned buffer");
+  return DAGPU_OK;
+}
+
+}  // namespace
+
+int dagpu_nmt_namespace_ranges_device(dagpu_ctx* ctx, uint32_t k, size_t n_q, const uint8_t* namespaces,
+                                      const uint8_t* d_row_nodes, int32_t* ranges_out, int64_t* counts_out,
+                                      void* d_workspace, void* stream) {
+  if (!ctx) return DAGPU_ERR_ARG;
+  int rc = check_k(ctx, k);
+  if (rc) return rc;
+  if (n_q == 0) {
+    if (counts_out) counts_out[0] = counts_out[1] = counts_out[2] = counts_out[3] = 0;
+    return DAGPU_OK;
+  }
+  if (!ranges_out || !counts_out) return set_err(ctx, DAGPU_ERR_ARG, "dagpu_nmt_namespace_ranges_device: null buffer");
+  rc = ns_common_check(ctx, "dagpu_nmt_namespace_ranges_device", namespaces, d_row_nodes, d_workspace);
+  if (rc) return rc;
+  return ns_search(ctx, k, n_q, namespaces, d_row_nodes, ranges_out, counts_out, (uint8_t*)d_workspace,
+                   (hipStream_t)stream);
+}
+
+int dagpu_nmt_prove_namespace_batch_device(dagpu_ctx* ctx, uint32_t k, size_t n_q, const uint8_t* namespaces,
+                                           const uint8_t* d_eds, const uint8_t* d_row_nodes, uint8_t* d_nodes_out,
+                                           size_t nodes_cap, uint8_t* d_ns_out, uint8_t* d_shares_out,
+                                           size_t shares_cap, uint8_t* d_leaf_hashes_out, size_t leaf_hashes_cap,
+                                           int64_t* desc_out, int32_t* pairs_out, size_t proofs_cap,
+                                           int64_t* counts_out, void* d_workspace, void* stream) {
+  if (!ctx) return DAGPU_ERR_ARG;
+  int rc = check_k(ctx, k);
+  if (rc) return rc;
+  if (n_q == 0) {
+    if (counts_out) counts_out[0] = counts_out[1] = counts_out[2] = counts_out[3] = 0;
+    return DAGPU_OK;
+  }
+  const char* who = "dagpu_nmt_prove_namespace_batch_device";
+  if (!counts_out || !d_ns_out || !d_eds || (nodes_cap && !d_nodes_out) || (shares_cap && !d_shares_out) ||
+      (leaf_hashes_cap && !d_leaf_hashes_out) || (proofs_cap && (!desc_out || !pairs_out)))
+    return set_err(ctx, DAGPU_ERR_ARG, std::string(who) + ": null buffer");
+  rc = ns_common_check(ctx, who, namespaces, d_row_nodes, d_workspace);
+  if (rc) return rc;
+  if ((((uintptr_t)d_eds | (uintptr_t)d_shares_out) & 15) != 0 ||
+      ((((uintptr_t)d_nodes_out) | (uintptr_t)d_leaf_hashes_out) & 1) != 0)
+    return set_err(ctx, DAGPU_ERR_ARG, std::string(who) + ": misaligned buffer");
+  hipStream_t s = (hipStream_t)stream;
+  uint8_t* ws = (uint8_t*)d_workspace;
+  const size_t w = 2 * (size_t)k, pairs = n_q * w;
+  const int m = prove_log2((uint32_t)w);
+  std::vector<int32_t> ranges(pairs * kNsRangeWords);
+  int64_t need[4];
+  rc = ns_search(ctx, k, n_q, namespaces, d_row_nodes, ranges.data(), need, ws, s);
+  if (rc) return rc;
+  memcpy(counts_out, need, sizeof need);
+  if ((uint64_t)need[0] > proofs_cap || (uint64_t)need[1] > leaf_hashes_cap || (uint64_t)need[2] > nodes_cap ||
+      (uint64_t)need[3] > shares_cap)
+    return set_err(ctx, DAGPU_ERR_ARG, std::string(who) + ": a capacity is too small (proofs " +
+                                           std::to_string(need[0]) + ", leaf hashes " + std::to_string(need[1]) +
+                                           ", nodes " + std::to_string(need[2]) + ", cells " +
+                                           std::to_string(need[3]) + " needed)");
+  const size_t n = (size_t)need[0], n_abs = (size_t)need[1];
+  if (n) {
+    // device image: packed requests (n) | node_off (n + 1) | leaf_off (n + 1) | absence records (n_abs)
+    std::vector<int64_t> meta(3 * n + 2 + n_abs);
+    int64_t* node_off = meta.data() + n;
+    int64_t* leaf_off = node_off + (n + 1);
+    int64_t* abs_rec = leaf_off + (n + 1);
+    int64_t nodes = 0, cells = 0;
+    size_t i = 0, j = 0;
+    for (size_t p = 0; p < pairs; p++) {
+      const int32_t* r = ranges.data() + p * kNsRangeWords;
+      if (r[0] == kNsOutside) continue;
+      const int64_t q = (int64_t)(p / w), row = (int64_t)(p % w);
+      const int64_t req[kProveReqWords] = {0, row, r[1], r[2]};
+      const int64_t nn = prove_node_count(m, (uint32_t)r[1], (uint32_t)r[2]);
+      const bool absent = r[0] == kNsAbsent;
+      meta[i] = (int64_t)prove_pack_req(req);
+      node_off[i] = nodes;
+      leaf_off[i] = cells;
+      int64_t* d = desc_out + i * kPvDescNmtNs;
+      d[0] = r[1];
+      d[1] = r[2];
+      d[2] = absent ? 0 : r[2] - r[1];
+      d[3] = cells;
+      d[4] = nn;
+      d[5] = nodes;
+      d[6] = q;
+      d[7] = row;
+      d[8] = absent ? (int64_t)j : -1;
+      pairs_out[2 * i] = (int32_t)q;
+      pairs_out[2 * i + 1] = (int32_t)row;
+      if (absent) abs_rec[j++] = row * (int64_t)w + r[1];
+      nodes += nn;
+      if (!absent) cells += r[2] - r[1];
+      i++;
+    }
+    node_off[n] = nodes;
+    leaf_off[n] = cells;
+    uint8_t* d_meta = ws + align256(32 * n_q) + align256(pairs * kNsRangeWords * sizeof(int32_t));
+    HIP_TRY(ctx, hipMemcpyAsync(d_meta, meta.data(), meta.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));  // `meta` may go
+    ProveArgs a{};
+    a.n = (long)n;
+    a.w = (int)w;
+    a.logw = m;
+    a.req = (const uint64_t*)d_meta;
+    a.node_off = (const int64_t*)d_meta + n;
+    a.leaf_off = a.node_off + (n + 1);
+    a.n_nodes = (long)nodes;
+    a.n_leaves = (long)cells;
+    a.row_nodes = d_row_nodes;
+    a.eds = d_eds;
+    a.nodes_out = d_nodes_out;
+    a.shares_out = d_shares_out;
+    HIP_TRY(ctx, launch_prove_emit(a, s));
+    HIP_TRY(ctx, launch_prove_shares(a, s));
+    HIP_TRY(ctx, launch_ns_leaf_nodes(d_row_nodes, a.leaf_off + (n + 1), (long)n_abs, d_leaf_hashes_out, s));
+  }
+  // the query namespaces, as uploaded for the search (zero padded to 32 B each)
+  HIP_TRY(ctx, hipMemcpy2DAsync(d_ns_out, kNsSize, ws, 32, kNsSize, n_q, hipMemcpyDeviceToDevice, s));
   return DAGPU_OK;
 }
 

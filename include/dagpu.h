@@ -542,6 +542,114 @@ int dagpu_nmt_prove_batch_device(dagpu_ctx* ctx, uint32_t k, size_t n, const int
                                  int64_t* desc_out, size_t* n_nodes_total, void* d_workspace,
                                  void* stream);
 
+/* ---- Namespace proofs: ProveNamespace / VerifyNamespace -------------------
+ * "Every share of namespace N in this square, with a proof that nothing was
+ * left out": nmt ProveNamespace, Proof.VerifyNamespace and absence proofs (what
+ * celestia-node's GetSharesByNamespace serves per row).  nmt is not part of the
+ * reference tree (it only calls ProveRange, pkg/proof/proof.go:140): like
+ * VerifyInclusion above, the rules are recalled from nmt v0.20.0 and are
+ * "parity unpinned".  THIS BLOCK IS THEIR SPECIFICATION.
+ *
+ * Namespaces are 29 bytes compared bytewise, IgnoreMaxNamespace is on, nodes
+ * are 90 B (min | max | digest).  Leaves are given WITHOUT the namespace the
+ * tree prepends, as for dagpu_nmt_verify_inclusion; a leaf is hashed as
+ * 0x00 | nid | leaf.
+ *
+ * ProveNamespace(tree, nid) on one full tree of 2k leaves with root R:
+ *   1 nid < R.min or R.max < nid: the EMPTY proof, start = end = 0, no nodes,
+ *     no leaf hash.  R.max is the stored one: in rows < k it ignores the parity
+ *     leaves, so the parity namespace is outside those rows and is the whole
+ *     row in rows >= k.
+ *   2 leaves with ns == nid exist (contiguous, [s, e)): the PRESENCE proof,
+ *     range [s, e) with the ProveRange(s, e) nodes, no leaf hash.
+ *   3 otherwise the ABSENCE proof: s = the first leaf with ns > nid, range
+ *     [s, s+1) with the ProveRange(s, s+1) nodes, and leafHash = the 90-B leaf
+ *     node of s.  No leaf data is carried.
+ *
+ * VerifyNamespace(proof, nid, leaves, root):
+ *   1 empty form (start == end, no nodes, no leaf hash): valid iff there are no
+ *     leaves and nid < root.min or root.max < nid.
+ *   2 else start < 0, start >= end or end > 2^62 fail the proof.
+ *   3 absence (a leaf hash is given): invalid with any leaves, with
+ *     end - start != 1, or unless nid < leafHash.min; the one leaf node of the
+ *     fold is leafHash itself.
+ *   4 presence: invalid unless n_leaves == end - start; leaf nodes are
+ *     nid | nid | SHA256(0x00 | nid | leaf).
+ *   5 the fold of dagpu_nmt_verify_inclusion, unchanged (same code).
+ *   6 completeness: every proof node consumed for a subtree left of the range
+ *     must have max < nid, every one consumed right of it (the leftover nodes
+ *     folded on the right included) nid < min.
+ * dagpu_nmt_verify_namespace is the host verifier (leaf_hash90 NULL unless
+ * absence); return codes as dagpu_nmt_verify_inclusion.
+ *
+ * Batched on the GPU: dagpu_nmt_verify_namespace_batch (host buffers) and
+ * dagpu_nmt_verify_namespace_batch_device mirror the two inclusion calls with
+ * 9-word descriptors: words 0-7 as DAGPU_NMT_DESC_WORDS, word 8 =
+ * leaf_hash_index into `leaf_hashes` (90 B each), -1 = none.  The descriptor
+ * checks are the same plus that index (< -1 or >= n_leaf_hashes):
+ * DAGPU_ERR_ARG, status untouched.  Proofs that rules 2-4 reject from the
+ * descriptor alone get DAGPU_ERR_PROOF with no device work; status[i] equals
+ * what dagpu_nmt_verify_namespace returns for proof i.  Stream and workspace
+ * contract as dagpu_nmt_verify_batch_device, with
+ * dagpu_nmt_verify_namespace_workspace_size(n, m), m >= the sum of n_leaves;
+ * d_leaves may be a resident EDS.
+ *
+ * From a resident square, ROW trees only (column trees are out of scope: a
+ * namespace is contiguous along rows of Q0 and that is what nodes serve):
+ * dagpu_nmt_namespace_ranges_device classifies n_q namespaces (HOST, 29 B
+ * each) against every row tree of the row store d_row_nodes
+ * (dagpu_row_nodes_device; root records in its top level, leaf namespaces in
+ * level 0): ranges_out (HOST) gets n_q x 2k x { kind, start, end } int32, kind
+ * DAGPU_NS_OUTSIDE / PRESENT / ABSENT (start = end = 0 outside); counts_out[4]
+ * = { proofs with kind != 0, absence proofs, proof nodes, proven cells }.  It
+ * synchronises `stream` once, for the read-back.
+ * dagpu_nmt_prove_namespace_batch_device searches the same way, lays the
+ * proofs with kind != 0 out in (query, row) order and enqueues: their nodes
+ * (d_nodes_out, 90 B each, 2-B aligned), the proven shares of presence proofs
+ * (d_shares_out, 512 B each, 16-B aligned; d_eds is the square), the absence
+ * proofs' leaf hashes (d_leaf_hashes_out, level-0 nodes packed 90 B, 2-B
+ * aligned) and d_ns_out = the n_q query namespaces.  On the HOST it writes one
+ * 9-word descriptor per proof (desc_out: ns_index = query, root_index = row
+ * into a row-roots table, n_leaves = 0 and leaf_hash_index = running count for
+ * absence) and pairs_out, { query, row } int32 per proof: the layout
+ * dagpu_nmt_verify_namespace_batch_device takes, and that call may follow on
+ * the same stream with no synchronisation.  Capacities are arguments
+ * (proofs_cap, nodes_cap, shares_cap, leaf_hashes_cap); when one is too small
+ * the call returns DAGPU_ERR_ARG, counts_out holds what is needed and every
+ * other output is untouched.  n_q = 0 is DAGPU_OK: counts_out = 0, nothing
+ * else written.  d_workspace (16-B aligned) of
+ * dagpu_nmt_namespace_workspace_size(k, n_q) bytes serves both calls. */
+#define DAGPU_NMT_NS_DESC_WORDS 9
+#define DAGPU_NS_OUTSIDE 0
+#define DAGPU_NS_PRESENT 1
+#define DAGPU_NS_ABSENT 2
+int dagpu_nmt_verify_namespace(const uint8_t* ns29, const uint8_t* leaves, size_t n, size_t leaf_len,
+                               int64_t start, int64_t end, const uint8_t* nodes, size_t nnodes,
+                               const uint8_t* leaf_hash90, const uint8_t* root90);
+int dagpu_nmt_verify_namespace_batch(dagpu_ctx* ctx, size_t n, const int64_t* desc, const uint8_t* namespaces,
+                                     size_t n_ns, const uint8_t* leaves, size_t n_leaves, size_t leaf_len,
+                                     const uint8_t* nodes, size_t n_nodes, const uint8_t* leaf_hashes,
+                                     size_t n_leaf_hashes, const uint8_t* roots, size_t n_roots,
+                                     int32_t* status);
+size_t dagpu_nmt_verify_namespace_workspace_size(size_t n, size_t n_leaves);
+int dagpu_nmt_verify_namespace_batch_device(dagpu_ctx* ctx, size_t n, const int64_t* desc,
+                                            const uint8_t* d_namespaces, size_t n_ns, const uint8_t* d_leaves,
+                                            size_t n_leaves, size_t leaf_len, const uint8_t* d_nodes,
+                                            size_t n_nodes, const uint8_t* d_leaf_hashes, size_t n_leaf_hashes,
+                                            const uint8_t* d_roots, size_t n_roots, int32_t* d_status,
+                                            void* d_workspace, void* stream);
+size_t dagpu_nmt_namespace_workspace_size(uint32_t k, size_t n_q);
+int dagpu_nmt_namespace_ranges_device(dagpu_ctx* ctx, uint32_t k, size_t n_q, const uint8_t* namespaces,
+                                      const uint8_t* d_row_nodes, int32_t* ranges_out, int64_t* counts_out,
+                                      void* d_workspace, void* stream);
+int dagpu_nmt_prove_namespace_batch_device(dagpu_ctx* ctx, uint32_t k, size_t n_q, const uint8_t* namespaces,
+                                           const uint8_t* d_eds, const uint8_t* d_row_nodes,
+                                           uint8_t* d_nodes_out, size_t nodes_cap, uint8_t* d_ns_out,
+                                           uint8_t* d_shares_out, size_t shares_cap,
+                                           uint8_t* d_leaf_hashes_out, size_t leaf_hashes_cap,
+                                           int64_t* desc_out, int32_t* pairs_out, size_t proofs_cap,
+                                           int64_t* counts_out, void* d_workspace, void* stream);
+
 /* ---- Square construction (host; pkg/square, app version 1) ---------------
  * square.Construct (pkg/square/square.go:22-63, builder.go): ntx txs packed
  * back to back in `txs` (tx_lens[i] bytes each; blob txs in the BlobTx proto
