@@ -68,6 +68,11 @@ EXPORTS = (
     "dagpu_repair_ex",
     "dagpu_square_construct",
     "dagpu_square_build",
+    "dagpu_square_plan",
+    "dagpu_square_plan_check",
+    "dagpu_square_plan_write_host",
+    "dagpu_square_write_workspace_size",
+    "dagpu_square_write_device",
     "dagpu_profile_enable",
     "dagpu_profile_read",
     "dagpu_profile_stages",
@@ -209,6 +214,12 @@ def lib() -> ctypes.CDLL:
         L.dagpu_repair_ex.argtypes = [vp, ctypes.c_uint32, vp, vp, vp, vp, vp]
         L.dagpu_square_construct.argtypes = [vp, vp, vp, sz, ctypes.c_uint32, ctypes.c_uint32, vp, sz, vp]
         L.dagpu_square_build.argtypes = [vp, vp, vp, sz, ctypes.c_uint32, ctypes.c_uint32, vp, sz, vp, vp]
+        L.dagpu_square_plan.argtypes = [vp, vp, vp, sz, ctypes.c_uint32, ctypes.c_uint32, vp, vp, sz, vp, vp]
+        L.dagpu_square_plan_check.argtypes = [vp, sz, sz]
+        L.dagpu_square_plan_write_host.argtypes = [vp, sz, vp, sz, vp, sz]
+        L.dagpu_square_write_workspace_size.argtypes = [sz, sz]
+        L.dagpu_square_write_workspace_size.restype = sz
+        L.dagpu_square_write_device.argtypes = [vp, ctypes.c_uint32, sz, vp, vp, vp, vp, sz, vp, sz, sz, vp, vp]
         L.dagpu_repair_batch_device_ex.argtypes = [vp, ctypes.c_uint32, sz, vp, vp, vp, vp, vp, vp,
                                                    vp, vp]
         L.dagpu_repair_start.argtypes = [vp, ctypes.c_uint32, sz, vp, vp, vp, vp, vp, vp, vp,

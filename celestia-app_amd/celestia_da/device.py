@@ -251,6 +251,52 @@ def nmt_verify_namespace_batch_device(desc, namespaces: torch.Tensor, leaves: to
     return status
 
 
+def write_squares_device(k: int, plans, srcs, out: torch.Tensor, square_stride: int, row_pitch: int,
+                         ctx: Optional[Context] = None, stream: Optional[torch.cuda.Stream] = None,
+                         lead: int = 0) -> None:
+    """dagpu_square_write_device: the squares of n plans (square.plan_native;
+    uint8 arrays) and their blocks' packed txs (srcs: n bytes-likes, uploaded
+    back to back behind `lead` unused bytes) written into `out` (cuda uint8),
+    square i at byte i * square_stride, rows row_pitch bytes apart.  Enqueued
+    on `stream`; returns once the plans and txs have left host memory."""
+    import numpy as np
+    c = ctx or default_context()
+    n, dev = len(plans), out.device
+    if len(srcs) != n:
+        raise ValueError("one packed txs buffer per plan")
+    if n == 0:
+        return
+    if out.dtype != torch.uint8 or not out.is_contiguous() or \
+            out.numel() < (n - 1) * square_stride + (k - 1) * row_pitch + k * 512:
+        raise ValueError("out must be a contiguous cuda uint8 tensor holding n squares at the given strides")
+    offs = np.zeros(n + 1, np.uint64)
+    offs[0] = lead
+    for i, b in enumerate(srcs):
+        offs[i + 1] = offs[i] + len(b)
+    total = int(offs[n])
+    host = torch.empty((max(total, 1),), dtype=torch.uint8).pin_memory()
+    hv = host.numpy()
+    for i, b in enumerate(srcs):
+        if len(b):
+            hv[int(offs[i]):int(offs[i + 1])] = np.frombuffer(b, np.uint8)
+    plans = [np.ascontiguousarray(p, dtype=np.uint8) for p in plans]
+    sizes = np.array([p.size for p in plans], np.uint64)
+    ptrs = np.array([_abi.addr(p) for p in plans], np.uint64)
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.stream(s):
+        d_src = host.to(dev, non_blocking=True)
+        ws = torch.empty((c._L.dagpu_square_write_workspace_size(n, int(sizes.sum())),), dtype=torch.uint8,
+                         device=dev)
+    rc = c._L.dagpu_square_write_device(c.handle, k, n, _abi.addr(ptrs), _abi.addr(sizes), _abi.addr(d_src),
+                                        _abi.addr(offs), total, _abi.addr(out), square_stride, row_pitch,
+                                        _abi.addr(ws), _stream_handle(s))
+    if rc != 0:
+        raise DAError(rc, c.last_error())
+    # the pinned staging buffer goes back to torch's host cache, which reuses
+    # it only after the copy queued above has run
+    del host
+
+
 class DeviceSquares:
     """n squares of width k resident on one GPU.
 
@@ -294,6 +340,45 @@ class DeviceSquares:
             self.q0().copy_(src)
         else:
             self.ods.view(self.n, self.k, self.k * 512).copy_(src)
+
+    def load_txs(self, blocks, stream: Optional[torch.cuda.Stream] = None, threads: int = 16,
+                 max_square_size: Optional[int] = None, threshold: Optional[int] = None) -> None:
+        """n blocks of raw txs (each a sequence of bytes) -> their squares where
+        extend() reads them, with no ODS on the host: every block is planned on
+        the host (square.plan_native's dagpu_square_plan, on a pool of at most
+        16 threads), txs and plans are uploaded and dagpu_square_write_device
+        writes self.ods, or Q0 of the EDS at the EDS row pitch when in_place.
+        Raises ShareError as square.construct_native does, and DAError when a
+        block's square width is not self.k (nothing is written then)."""
+        from concurrent.futures import ThreadPoolExecutor
+
+        from . import square as sq
+        if len(blocks) != self.n:
+            raise ValueError(f"{self.n} blocks expected, got {len(blocks)}")
+        if self.ods is None and not self.in_place:
+            raise ValueError("no ODS buffer: DeviceSquares(with_ods=False) takes its input through extend_from")
+        m = sq.SQUARE_SIZE_UPPER_BOUND if max_square_size is None else max_square_size
+        t = sq.SUBTREE_ROOT_THRESHOLD if threshold is None else threshold
+
+        def plan(txs):
+            buf, lens = sq._pack(txs)
+            k, p = sq._plan_packed(buf, lens, len(txs), m, t)
+            return k, p, buf[:int(lens.sum())]
+
+        workers = max(1, min(16, int(threads), self.n))
+        if workers == 1:
+            planned = [plan(b) for b in blocks]
+        else:
+            with ThreadPoolExecutor(workers) as pool:
+                planned = list(pool.map(plan, blocks))
+        for i, (k, _, _) in enumerate(planned):
+            if k != self.k:
+                raise DAError(_abi.ERR_ARG, f"block {i} has square width {k}, these squares have width {self.k}")
+        w = 2 * self.k
+        out, stride, pitch = ((self.eds, w * w * 512, w * 512) if self.in_place
+                              else (self.ods, self.k * self.k * 512, self.k * 512))
+        write_squares_device(self.k, [p for _, p, _ in planned], [b for _, _, b in planned], out.view(-1), stride,
+                             pitch, ctx=self.ctx, stream=stream)
 
     def _ck(self, rc: int) -> None:
         if rc != 0:

@@ -394,6 +394,90 @@ def build_native(txs: Sequence[bytes], max_square_size: int = SQUARE_SIZE_UPPER_
     return k, ods, normal + blob
 
 
+# ---- plan on the host, write on the device (csrc/square.cpp dagpu_square_plan,
+# csrc/square_write.hip dagpu_square_write_device) -------------------------------
+
+PLAN_GUESS = 64 << 10  # first plan buffer; a full 4,000-tx block needs ~0.2 MB and asks again
+
+
+def _plan_packed(buf, lens, ntx: int, max_square_size: int, threshold: int, kept=None):
+    """dagpu_square_plan on txs already packed (buf, lens): (k, plan as a uint8
+    array).  Raises as _native does."""
+    import ctypes
+
+    import numpy as np
+
+    from . import _abi
+    L = _abi.lib()
+    k, need = ctypes.c_uint32(0), ctypes.c_size_t(0)
+    plan = np.empty(PLAN_GUESS, np.uint8)
+    for _ in range(2):
+        rc = L.dagpu_square_plan(None, _abi.addr(buf), _abi.addr(lens), ntx, max_square_size, threshold,
+                                 _abi.addr(kept), _abi.addr(plan), plan.size, ctypes.addressof(need),
+                                 ctypes.addressof(k))
+        if rc == _abi.ERR_ARG and need.value > plan.size:
+            plan = np.empty(need.value, np.uint8)  # the call reported the size
+            continue
+        break
+    if rc != 0:
+        msg = L.dagpu_last_error(None).decode()
+        raise ShareError(msg) if rc == _abi.ERR_SQUARE else ValueError(f"dagpu_square_plan: status {rc}: {msg}")
+    return int(k.value), plan[:need.value]
+
+
+def plan_native(txs: Sequence[bytes], max_square_size: int = SQUARE_SIZE_UPPER_BOUND,
+                threshold: int = SUBTREE_ROOT_THRESHOLD, build: bool = False):
+    """The layout half of construct_native / build_native (dagpu_square_plan):
+    (k, plan bytes) or, with build=True, (k, plan bytes, kept txs).  The plan
+    refers to the txs packed back to back (b"".join(txs)); write_plan_host or
+    construct_device turn it into the ODS.  Raises as construct_native does."""
+    import numpy as np
+    buf, lens = _pack(txs)
+    if not build:
+        return _plan_packed(buf, lens, len(txs), max_square_size, threshold)
+    kept = np.zeros(max(1, len(txs)), np.uint8)
+    k, plan = _plan_packed(buf, lens, len(txs), max_square_size, threshold, kept)
+    normal = [t for i, t in enumerate(txs) if kept[i] and not btx.unmarshal_blob_tx(t)[1]]
+    blob = [t for i, t in enumerate(txs) if kept[i] and btx.unmarshal_blob_tx(t)[1]]
+    return k, plan, normal + blob
+
+
+def write_plan_host(plan, txs: Sequence[bytes], k: int, row_pitch: Optional[int] = None, out=None):
+    """dagpu_square_plan_write_host: the ODS of a plan and its txs, computed
+    share by share with the function the kernel runs.  Returns `out` (a uint8
+    array of k rows row_pitch bytes apart, default packed)."""
+    import numpy as np
+
+    from . import _abi
+    L = _abi.lib()
+    src = np.frombuffer(b"".join(bytes(t) for t in txs), np.uint8)
+    pitch = k * sh.SHARE_SIZE if row_pitch is None else row_pitch
+    if out is None:
+        out = np.empty(k * pitch, np.uint8)
+    plan = np.ascontiguousarray(plan, dtype=np.uint8)
+    rc = L.dagpu_square_plan_write_host(_abi.addr(plan), plan.size, _abi.addr(src) if src.size else None, src.size,
+                                        _abi.addr(out), pitch)
+    if rc != 0:
+        raise ValueError(f"dagpu_square_plan_write_host: status {rc}: {L.dagpu_last_error(None).decode()}")
+    return out
+
+
+def construct_device(txs: Sequence[bytes], device: int = 0, ctx=None,
+                     max_square_size: int = SQUARE_SIZE_UPPER_BOUND, threshold: int = SUBTREE_ROOT_THRESHOLD):
+    """square.Construct with the ODS assembled on the GPU: plan on the host,
+    upload the raw txs and the plan, write the shares in HBM
+    (dagpu_square_write_device).  Returns (k, ODS as a (k*k*512,) cuda uint8
+    tensor), byte-identical to construct_native(txs)."""
+    import torch
+
+    from .device import write_squares_device
+    k, plan = plan_native(txs, max_square_size, threshold)
+    ods = torch.empty((k * k * sh.SHARE_SIZE,), dtype=torch.uint8, device=torch.device("cuda", device))
+    write_squares_device(k, [plan], [b"".join(bytes(t) for t in txs)], ods, k * k * sh.SHARE_SIZE,
+                         k * sh.SHARE_SIZE, ctx=ctx)
+    return k, ods
+
+
 def tx_share_range(txs: Sequence[bytes], tx_index: int, app_version: int = LATEST_VERSION) -> Range:
     return Builder(square_size_upper_bound(app_version), app_version, *txs).find_tx_share_range(tx_index)
 

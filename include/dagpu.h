@@ -672,6 +672,62 @@ int dagpu_square_build(dagpu_ctx* ctx, const uint8_t* txs, const uint64_t* tx_le
                        uint32_t max_square_size, uint32_t subtree_root_threshold, uint8_t* ods_out,
                        size_t ods_cap, uint32_t* square_size, uint8_t* kept);
 
+/* ---- Square construction on the device: plan on the host, write in HBM ----
+ * The entry of block replay is txs, not an ODS (app/extend_block.go:14-22:
+ * square.Construct, then da.ExtendShares; app/prepare_proposal.go:87-107 and
+ * app/process_proposal.go:135-161 start from txs too).  These calls split
+ * square.Construct / square.Build (pkg/square/square.go:22-63, builder.go
+ * Export, WriteSquare) into the layout, decided on the host, and the writing
+ * of the k*k shares (pkg/shares/split_compact_shares.go, split_sparse_shares.go,
+ * padding.go), done by one function per share that the host executor and the
+ * kernel share (csrc/square_write.hpp).
+ *
+ * dagpu_square_plan: the arguments, checks, return codes and messages of
+ * dagpu_square_construct (kept == NULL) or dagpu_square_build (kept != NULL,
+ * filled as there), but the result is a plan: a relocatable blob of tables
+ * with no pointers, whose source references are offsets into `txs`.  It copies
+ * no payload byte.  *plan_bytes and *square_size are set even when plan_out
+ * (plan_cap bytes, 4-B aligned) is too small, which returns DAGPU_ERR_ARG.
+ * DAGPU_ERR_UNSUPPORTED for txs of 2 GiB or more, or a square wider than 1024.
+ * Thread-safe: blocks of a batch may be planned on several threads.
+ *
+ * dagpu_square_plan_check: every offset and range of a plan against its own
+ * size and src_bytes of txs, the runs covering shares 0 .. k*k-1 once and in
+ * order, and the order of the tables the writer searches; DAGPU_ERR_ARG on any
+ * violation (message: dagpu_last_error(NULL)).  The writers trust a plan only
+ * after it: both run it first.
+ *
+ * dagpu_square_plan_write_host: the square of a plan and its txs, row r at
+ * ods_out + r * row_pitch (row_pitch >= k*512; bytes between rows untouched). */
+int dagpu_square_plan(dagpu_ctx* ctx, const uint8_t* txs, const uint64_t* tx_lens, size_t ntx,
+                      uint32_t max_square_size, uint32_t subtree_root_threshold, uint8_t* kept, uint8_t* plan_out,
+                      size_t plan_cap, size_t* plan_bytes, uint32_t* square_size);
+int dagpu_square_plan_check(const uint8_t* plan, size_t plan_bytes, size_t src_bytes);
+int dagpu_square_plan_write_host(const uint8_t* plan, size_t plan_bytes, const uint8_t* txs, size_t src_bytes,
+                                 uint8_t* ods_out, size_t row_pitch);
+/* n planned squares of one width k written in HBM by one kernel (one wave per
+ * share).  plans[i] / plan_bytes[i] (HOST) is block i's plan, its packed txs
+ * lie at d_src + src_offs[i] (src_offs: n + 1 HOST offsets, ascending, the last
+ * <= src_bytes, the size of d_src); square i goes to d_ods + i * square_stride
+ * with rows row_pitch bytes apart: row_pitch = k*512 and square_stride =
+ * k*k*512 is the packed ODS batch, row_pitch = 2k*512 and square_stride =
+ * 4k*k*512 writes Q0 of an EDS batch in place, the zero-copy input of
+ * dagpu_extend_batch_device (d_ods = NULL).  d_ods, square_stride and row_pitch
+ * are multiples of 16; bytes outside each square's k x (k*512) window are not
+ * touched.  Every plan is checked (dagpu_square_plan_check) and must have width
+ * k, else DAGPU_ERR_ARG (the message names the block) and nothing is enqueued.
+ * d_workspace (16-B aligned, dagpu_square_write_workspace_size(n, sum of
+ * plan_bytes) bytes) receives the plans and must stay valid until the kernel
+ * has run; with NULL the library allocates it and the call also waits for the
+ * kernel.  The call returns after the upload of the plans has left host
+ * memory (plans, plan_bytes and src_offs may be freed at once) and, with a
+ * workspace, before the kernel has run: it is enqueued on `stream`. */
+size_t dagpu_square_write_workspace_size(size_t n, size_t plan_bytes_total);
+int dagpu_square_write_device(dagpu_ctx* ctx, uint32_t k, size_t n, const uint8_t* const* plans,
+                              const size_t* plan_bytes, const uint8_t* d_src, const size_t* src_offs,
+                              size_t src_bytes, uint8_t* d_ods, size_t square_stride, size_t row_pitch,
+                              void* d_workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
