@@ -1,46 +1,12 @@
-// kernels.hpp -- device kernel launchers shared by the C-ABI layer (dagpu.cpp).
+// kernels.hpp -- device kernel launchers shared by the C-ABI layer (dagpu.cpp, repair_host.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "da_sizes.hpp"
 #include "switches.hpp"
 
 namespace dagpu {
-
-constexpr int kShareSize = 512;
-constexpr int kNsSize = 29;
-constexpr int kNodeSize = 90;  // minNs(29) | maxNs(29) | sha256(32)
-constexpr int kDigest = 32;
-// Widest square: (2k)^2 x 512 B of EDS = 128 GiB at k = 8192 fits the 288 GB of
-// HBM, k = 16384 (512 GiB) does not.  GF(2^16) above k = 128; register-resident
-// kernels at k = 256 / 512, LDS-slice kernels (rs_gf16_wide.hip) above.
-constexpr int kMaxK = 8192;
-// Widest codec vector (rsmt2d.Codec Encode / Decode, dagpu_encode / dagpu_decode):
-// Leopard GF(2^16)'s whole field, k data + k parity = 65536 shards (klauspost
-// leopardFF16 rejects more; rsmt2d LeoRSCodec.MaxChunks = 32768 * 32768).  A
-// vector is k x shard bytes, so these widths fit one GPU even where the square
-// of the same width does not; the wide kernels serve k = 16384 / 32768 with
-// 2- / 1-symbol LDS slices (rs_gf16_wide.hip).
-constexpr int kMaxCodecK = 32768;
-// Widest split square (split.cpp, one oversized square over P GPUs): k = 16384,
-// whose 512 GiB EDS one GPU cannot hold, over P >= kMinWideSplitParts ranks
-// (P = 8: per rank a 64 GiB column slab, 32 GiB of row staging and send
-// block, ~38 GiB of forest records -- under 288 GB; P = 4 would not fit).
-constexpr int kMaxSplitK = 2 * kMaxK;
-constexpr int kMinWideSplitParts = 8;
-
-// Bytes of error-locator workspace per decoded vector.
-// Error-locator workspace per vector: GF(2^8) 256 B; GF(2^16) the n = 2k uint16
-// locators (4k B) and after them, at rs_err_tab_off(k), what the decoders'
-// per-element multiplies need, built once per erasure pattern by the locator
-// kernel (round 6) instead of in every decoder workgroup: at k = 256 / 512 the
-// n x 80-B image of the product tables (exp(errLoc) for a present element,
-// exp(-errLoc) for a missing one) that a half-lane decoder copies into LDS;
-// at k >= 1024 the n x 32-B basis products (1 << b) * that factor, b < 16, from
-// which a wide decoder workgroup builds an element's table without gathers.
-constexpr long rs_err_tab_off(int k) { return 4L * k; }
-constexpr long rs_err_elem_bytes(int k) { return k <= 1024 ? 80 : 32; }
-constexpr long rs_err_bytes(int k) { return k <= 128 ? 256 : 4L * k + 2L * k * rs_err_elem_bytes(k); }
 
 // Per-square status bits written by the kernels (0 = OK).
 constexpr int kStatusPushOrder = 1;
@@ -65,7 +31,7 @@ struct EncodeArgs {
   int32_t* mismatch;
   int mismatch_bit;
   int32_t* mismatch_vec;  // optional: mismatch_vec[square * nvec + vec] = 1 on a difference
-  // Fill mode (Repair, dagpu.cpp repair_device): a vector whose data half is
+  // Fill mode (Repair, repair_host.cpp round_fills): a vector whose data half is
   // complete is rebuilt by encoding that half.  A parity shard is stored only
   // where out_present[sq * op_sq_stride + vec * op_vec_stride + j * op_shard_stride]
   // is 0; a given (present) one that differs from the encoding sets
@@ -169,7 +135,7 @@ struct DecodeArgs {
   // Optional (launch_vec_count): vec_counts[v] = present data shards | present
   // shards << 16 (Repair plan).
   int32_t* vec_counts;
-  // Optional vector selection (exact-order Repair, dagpu.cpp): only vectors v
+  // Optional vector selection (exact-order Repair, repair_host.cpp): only vectors v
   // with sel_level[v] == sel_value are decodable in this pass.  Requires
   // err_key/err_head = NULL (an unselected head computes no locators).
   const int32_t* sel_level;
@@ -273,7 +239,7 @@ hipError_t launch_verify_roots(const uint8_t* exp_rr, const uint8_t* exp_cr, con
 // rebuilt index} (-1 = none / not known): the first pre-repair failure in the
 // order i = 0..2k-1 x {row root, col root, row parity, col parity}, else a
 // crossword failure (kRepByz, axis resolved by the host), else unrepairable
-// Repair shortcut plan for one round on one axis (see repair_device): every
+// Repair shortcut plan for one round on one axis (see repair_host.cpp crossword_round): every
 // decodable vector of the axis whose data half is complete moves from the
 // decoder (flags) to the fill encoder (fill[v] = 1, forward), and one whose
 // parity half is complete to the reverse fill (fill[v] = 2); pair_list /

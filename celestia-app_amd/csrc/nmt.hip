@@ -486,20 +486,15 @@ long nmt_level_fill_blocks() {
   return fill;
 }
 
-static size_t align256(size_t v) { return ws_align256(v); }
-
 size_t nmt_workspace_bytes(int k, long nsq) { return nmt_ws_bytes(k, nsq); }
 
 void nmt_workspace_carve(SquareArgs& a, void* ws) {
-  const size_t w = 2 * (size_t)a.k;
+  const NmtCarve c = nmt_carve(a.k, a.nsq);  // pipe_carve.hpp: the one list of regions
   uint8_t* p = (uint8_t*)ws;
-  a.digests = p;
-  p += align256(w * w * kDigest * a.nsq);
-  a.ns_table = p;
-  p += align256((size_t)a.k * a.k * 32 * a.nsq);
-  a.rec_a = p;
-  p += align256(a.nsq * 2 * w * (w / 2) * 48);
-  a.rec_b = p;
+  a.digests = p + c.digests.off;
+  a.ns_table = p + c.ns_table.off;
+  a.rec_a = p + c.rec_a.off;
+  a.rec_b = p + c.rec_b.off;
 }
 
 static bool dah_split_enabled() {  // DAGPU_DAH_SPLIT=0: one workgroup per square always (A/B)

@@ -33,15 +33,35 @@ inline size_t nmt_level_rec_bytes(int k, int L) {
   return 2 * w * (w >> L) * 48;
 }
 
+// One region of a workspace: byte offset from its base and the bytes its
+// users address (the next region starts at the following multiple of 256).
+struct WsRegion {
+  size_t off, bytes;
+};
+
 // the unsliced layout: digests | ns_table | rec_a (level 1) | rec_b (level 2)
-inline size_t nmt_ws_bytes(int k, long nsq) {
+struct NmtCarve {
+  WsRegion digests, ns_table, rec_a, rec_b;
+  size_t end;
+};
+
+inline NmtCarve nmt_carve(int k, long nsq) {
+  NmtCarve c{};
   const size_t w = 2 * (size_t)k;
-  const size_t dig = ws_align256(w * w * 32 * nsq);
-  const size_t ns = ws_align256((size_t)k * k * 32 * nsq);
-  const size_t ra = ws_align256(nsq * 2 * w * (w / 2) * 48);
-  const size_t rb = ws_align256(nsq * 2 * w * (w / 4 > 0 ? w / 4 : 1) * 48);
-  return dig + ns + ra + rb;
+  size_t p = 0;
+  auto take = [&](WsRegion& r, size_t want) {
+    r = {p, want};
+    p += ws_align256(want);
+  };
+  take(c.digests, w * w * 32 * nsq);
+  take(c.ns_table, (size_t)k * k * 32 * nsq);
+  take(c.rec_a, nsq * 2 * w * (w / 2) * 48);
+  take(c.rec_b, nsq * 2 * w * (w / 4 > 0 ? w / 4 : 1) * 48);
+  c.end = p;
+  return c;
 }
+
+inline size_t nmt_ws_bytes(int k, long nsq) { return nmt_carve(k, nsq).end; }
 
 // Last tree level that still runs per slice: a level is deferred to the
 // batch-wide launch when its launch over a slice of m squares has fewer

@@ -1,6 +1,6 @@
 // repair.hip -- device helpers for rsmt2d ExtendedDataSquare.Repair (v0.11.0):
 // axis completeness, root verification and status mapping.  The decode itself
-// is rs_decode.hip; the crossword schedule is driven from dagpu.cpp.
+// is rs_decode.hip; the crossword schedule is driven from repair_host.cpp.
 //
 // Reference semantics: prerepairSanityCheck rejects a complete
 // axis whose root differs from the given one ("bad root input") or whose parity
@@ -175,7 +175,7 @@ hipError_t launch_verify_roots(const uint8_t* exp_rr, const uint8_t* exp_cr, con
 // oracle (orc_repair) follows too.  A root failure is "bad root input: <axis>
 // <i>", a parity failure ErrByzantineData{axis, i, that axis' shares}.  Then
 // the crossword: a failing rebuilt axis (kRepByz) is ErrByzantineData whose
-// axis and index the host resolves in rsmt2d's sequential order (dagpu.cpp
+// axis and index the host resolves in rsmt2d's sequential order (repair_host.cpp
 // exact_repair); then "no progress" (ErrUnrepairableDataSquare).
 __global__ __launch_bounds__(256) void finalize_repair_kernel(const int32_t* bits, const int32_t* complete_before,
                                                               const int32_t* root_bad, const int32_t* parity_bad,
@@ -253,7 +253,7 @@ hipError_t launch_restore_presence(uint8_t* present, const uint8_t* p0, const in
 
 // ---------------------------------------------------------------------------
 // Repair shortcut (round 3): fill route and deferral, see kernels.hpp PlanArgs
-// and dagpu.cpp repair_device.  A decode rebuilds a vector as the unique
+// and repair_host.cpp crossword_round.  A decode rebuilds a vector as the unique
 // codeword through its >= k given shares; when its data half (indices < k) is
 // complete that codeword is Encode(data half), which the fill encoder computes
 // for a fraction of the decoder's work (IFFT_k + FFT_k against the decoder's

@@ -1,6 +1,6 @@
 // runtime.hpp -- internal host runtime shared by the C-ABI translation units
-// (dagpu.cpp, trees.cpp, split.cpp): the context, device buffers, error
-// helpers and the per-kernel profiling bracket.
+// (dagpu.cpp, repair_host.cpp, trees.cpp, split.cpp): the context, device
+// buffers, error helpers and the per-kernel profiling bracket.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -148,6 +148,9 @@ struct dagpu_ctx {
 
 constexpr size_t kSS = dagpu::kShareSize;
 
+inline size_t eds_bytes(uint64_t k) { return 4ull * k * k * kSS; }
+inline size_t ods_bytes(uint64_t k) { return 1ull * k * k * kSS; }
+
 inline bool is_pow2(uint64_t v) { return v != 0 && (v & (v - 1)) == 0; }
 
 // The calling thread's own last failure (errno-like), so that a thread that
@@ -217,6 +220,14 @@ hipEvent_t ev_take(dagpu_ctx* c);
 void ev_give(dagpu_ctx* c, hipEvent_t e);
 hipStream_t side_stream(dagpu_ctx* ctx, hipStream_t s, int which = 0);
 size_t pipe_slices(dagpu_ctx* ctx, uint32_t k, size_t n);
+// dagpu.cpp: leaves, trees and (d_dah != NULL) the DAH of n squares; the
+// completion wait of a host-path call (spin: poll the stream).
+int enqueue_roots(dagpu_ctx* ctx, uint32_t k, size_t n, const uint8_t* d_eds, uint8_t* d_rr, uint8_t* d_cr,
+                  uint8_t* d_dah, int32_t* d_status, void* d_ws, hipStream_t s);
+hipError_t wait_stream(hipStream_t s, bool spin);
+// repair_host.cpp: "data half of every vector of this axis in, parity half
+// out" over n resident EDS (axis 0 = rows, 1 = columns).
+EncodeArgs axis_encode_args(uint32_t k, size_t n, uint8_t* d_eds, int axis);
 }  // namespace dagpu
 
 inline hipEvent_t pool_get(dagpu_ctx* c) {

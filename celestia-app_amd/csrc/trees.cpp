@@ -45,6 +45,7 @@
 #include "kernels.hpp"
 #include "host_sha256.hpp"
 #include "ns_find.hpp"
+#include "pipe_carve.hpp"
 #include "proof_verify.hpp"
 #include "prove_layout.hpp"
 #include "runtime.hpp"
@@ -209,8 +210,6 @@ int nmt_fold_verify(const uint8_t* lh, size_t n, int64_t start, int64_t end, con
 
 // ---- batched proof verification (proof_verify.hip) ----
 
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // off >= 0, cnt >= 0 and [off, off + cnt) inside [0, total)
 bool pv_span_ok(int64_t off, int64_t cnt, size_t total) {
   return off >= 0 && cnt >= 0 && (uint64_t)off <= (uint64_t)total && (uint64_t)cnt <= (uint64_t)total - (uint64_t)off;
@@ -275,7 +274,7 @@ int pv_check_nmt(dagpu_ctx* ctx, size_t n, const int64_t* desc, size_t n_ns, siz
 }
 
 size_t pv_nmt_meta_bytes(size_t n, int words = kPvDescNmt) {
-  return align256((n * words + 2 * (n + 1)) * sizeof(int64_t));
+  return ws_align256((n * words + 2 * (n + 1)) * sizeof(int64_t));
 }
 
 // Upload the plan and enqueue the leaf and fold passes.  Returns once the
@@ -494,7 +493,7 @@ int dagpu_col_nodes_device(dagpu_ctx* ctx, uint32_t k, const uint8_t* d_row_node
 
 size_t dagpu_nmt_prove_workspace_size(size_t n) {
   // packed requests (n) | node_off (n + 1) | leaf_off (n + 1), 8 B each
-  return align256((3 * n + 2) * sizeof(int64_t)) + 256;
+  return ws_align256((3 * n + 2) * sizeof(int64_t)) + 256;
 }
 
 int dagpu_nmt_prove_batch_device(dagpu_ctx* ctx, uint32_t k, size_t n, const int64_t* req, const uint8_t* d_eds,
@@ -701,8 +700,8 @@ int dagpu_nmt_verify_batch(dagpu_ctx* ctx, size_t n, const int64_t* desc, const 
   hipStream_t s = ctx->stream;
   const size_t b_ns = n_ns * kNsSize, b_lv = n_leaves * leaf_len, b_nd = n_nodes * kNodeSize,
                b_rt = n_roots * kNodeSize;
-  const size_t o_ns = 0, o_lv = o_ns + align256(b_ns), o_nd = o_lv + align256(b_lv), o_rt = o_nd + align256(b_nd),
-               o_st = o_rt + align256(b_rt), o_ws = o_st + align256(4 * n);
+  const size_t o_ns = 0, o_lv = o_ns + ws_align256(b_ns), o_nd = o_lv + ws_align256(b_lv), o_rt = o_nd + ws_align256(b_nd),
+               o_st = o_rt + ws_align256(b_rt), o_ws = o_st + ws_align256(4 * n);
   const size_t ws = pv_nmt_meta_bytes(n) + (size_t)kRecNmt * (size_t)(plan.n_records + plan.n_stack) + 256;
   PvScratch m;
   HIP_TRY(ctx, hipMalloc(&m.p, o_ws + ws));
@@ -766,8 +765,8 @@ int dagpu_nmt_verify_namespace_batch(dagpu_ctx* ctx, size_t n, const int64_t* de
   hipStream_t s = ctx->stream;
   const size_t b_ns = n_ns * kNsSize, b_lv = n_leaves * leaf_len, b_nd = n_nodes * kNodeSize,
                b_lh = n_leaf_hashes * kNodeSize, b_rt = n_roots * kNodeSize;
-  const size_t o_ns = 0, o_lv = o_ns + align256(b_ns), o_nd = o_lv + align256(b_lv), o_lh = o_nd + align256(b_nd),
-               o_rt = o_lh + align256(b_lh), o_st = o_rt + align256(b_rt), o_ws = o_st + align256(4 * n);
+  const size_t o_ns = 0, o_lv = o_ns + ws_align256(b_ns), o_nd = o_lv + ws_align256(b_lv), o_lh = o_nd + ws_align256(b_nd),
+               o_rt = o_lh + ws_align256(b_lh), o_st = o_rt + ws_align256(b_rt), o_ws = o_st + ws_align256(4 * n);
   const size_t ws = pv_nmt_meta_bytes(n, kPvDescNmtNs) + (size_t)kRecNmt * (size_t)(plan.n_records + plan.n_stack) + 256;
   PvScratch m;
   HIP_TRY(ctx, hipMalloc(&m.p, o_ws + ws));
@@ -797,8 +796,8 @@ size_t dagpu_nmt_namespace_workspace_size(uint32_t k, size_t n_q) {
   const size_t w = 2 * (size_t)k, pairs = n_q * w;
   // padded queries | ranges of every (query, row) | then, for the proof call:
   // packed requests, node and leaf offsets and absence records of <= pairs proofs
-  return align256(32 * n_q) + align256(pairs * kNsRangeWords * sizeof(int32_t)) +
-         align256((4 * pairs + 2) * sizeof(int64_t)) + 256;
+  return ws_align256(32 * n_q) + ws_align256(pairs * kNsRangeWords * sizeof(int32_t)) +
+         ws_align256((4 * pairs + 2) * sizeof(int64_t)) + 256;
 }
 
 namespace {
@@ -811,7 +810,7 @@ int ns_search(dagpu_ctx* ctx, uint32_t k, size_t n_q, const uint8_t* namespaces,
   const int m = prove_log2((uint32_t)w);
   std::vector<uint8_t> padded(32 * n_q, 0);
   for (size_t q = 0; q < n_q; q++) memcpy(&padded[32 * q], namespaces + q * kNsSize, kNsSize);
-  int32_t* d_ranges = (int32_t*)(d_ws + align256(32 * n_q));
+  int32_t* d_ranges = (int32_t*)(d_ws + ws_align256(32 * n_q));
   HIP_TRY(ctx, hipMemcpyAsync(d_ws, padded.data(), padded.size(), hipMemcpyHostToDevice, s));
   NsFindArgs a{};
   a.n_q = (long)n_q;
@@ -942,7 +941,7 @@ int dagpu_nmt_prove_namespace_batch_device(dagpu_ctx* ctx, uint32_t k, size_t n_
     }
     node_off[n] = nodes;
     leaf_off[n] = cells;
-    uint8_t* d_meta = ws + align256(32 * n_q) + align256(pairs * kNsRangeWords * sizeof(int32_t));
+    uint8_t* d_meta = ws + ws_align256(32 * n_q) + ws_align256(pairs * kNsRangeWords * sizeof(int32_t));
     HIP_TRY(ctx, hipMemcpyAsync(d_meta, meta.data(), meta.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
     HIP_TRY(ctx, hipStreamSynchronize(s));  // `meta` may go
     ProveArgs a{};
@@ -985,10 +984,10 @@ int dagpu_merkle_verify_batch(dagpu_ctx* ctx, size_t n, const int64_t* desc, con
   hipStream_t s = ctx->stream;
   const size_t b_ds = n * kPvDescMerkle * sizeof(int64_t), b_lv = n_leaves * leaf_len, b_lh = leaf_hashes ? 32 * n : 0,
                b_au = 32 * n_aunts, b_rt = 32 * n_roots;
-  const size_t o_ds = 0, o_lv = o_ds + align256(b_ds), o_lh = o_lv + align256(b_lv), o_au = o_lh + align256(b_lh),
-               o_rt = o_au + align256(b_au), o_st = o_rt + align256(b_rt);
+  const size_t o_ds = 0, o_lv = o_ds + ws_align256(b_ds), o_lh = o_lv + ws_align256(b_lv), o_au = o_lh + ws_align256(b_lh),
+               o_rt = o_au + ws_align256(b_au), o_st = o_rt + ws_align256(b_rt);
   PvScratch m;
-  HIP_TRY(ctx, hipMalloc(&m.p, o_st + align256(4 * n)));
+  HIP_TRY(ctx, hipMalloc(&m.p, o_st + ws_align256(4 * n)));
   uint8_t* d = (uint8_t*)m.p;
   HIP_TRY(ctx, hipMemcpyAsync(d + o_ds, desc, b_ds, hipMemcpyHostToDevice, s));
   if (b_lv) HIP_TRY(ctx, hipMemcpyAsync(d + o_lv, leaves, b_lv, hipMemcpyHostToDevice, s));
