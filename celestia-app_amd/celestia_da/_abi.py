@@ -73,6 +73,9 @@ EXPORTS = (
     "dagpu_square_plan_write_host",
     "dagpu_square_write_workspace_size",
     "dagpu_square_write_device",
+    "dagpu_blob_commitments_workspace_size",
+    "dagpu_blob_commitments_device",
+    "dagpu_square_plan_blobs",
     "dagpu_profile_enable",
     "dagpu_profile_read",
     "dagpu_profile_stages",
@@ -105,6 +108,10 @@ EXPORTS = (
     "dagpu_nmt_namespace_ranges_device",
     "dagpu_nmt_prove_namespace_batch_device",
 )
+
+# d_status bits of dagpu_blob_commitments_device
+COMMIT_MISMATCH = 1
+COMMIT_PUSH_ORDER = 2
 
 PROVE_REQ_WORDS = 4
 NMT_DESC_WORDS = 8
@@ -220,6 +227,11 @@ def lib() -> ctypes.CDLL:
         L.dagpu_square_write_workspace_size.argtypes = [sz, sz]
         L.dagpu_square_write_workspace_size.restype = sz
         L.dagpu_square_write_device.argtypes = [vp, ctypes.c_uint32, sz, vp, vp, vp, vp, sz, vp, sz, sz, vp, vp]
+        L.dagpu_blob_commitments_workspace_size.argtypes = [ctypes.c_uint32, sz, sz]
+        L.dagpu_blob_commitments_workspace_size.restype = sz
+        L.dagpu_blob_commitments_device.argtypes = [vp, ctypes.c_uint32, sz, sz, vp, vp, sz, sz, ctypes.c_uint32, vp, vp,
+                                                    vp, vp, vp, vp]
+        L.dagpu_square_plan_blobs.argtypes = [vp, sz, vp, sz, ctypes.POINTER(sz)]
         L.dagpu_repair_batch_device_ex.argtypes = [vp, ctypes.c_uint32, sz, vp, vp, vp, vp, vp, vp,
                                                    vp, vp]
         L.dagpu_repair_start.argtypes = [vp, ctypes.c_uint32, sz, vp, vp, vp, vp, vp, vp, vp,

@@ -297,6 +297,51 @@ def write_squares_device(k: int, plans, srcs, out: torch.Tensor, square_stride: 
     del host
 
 
+def blob_commitments_device(k: int, blobs, squares: torch.Tensor, square_stride: int, row_pitch: int,
+                            expected=None, threshold: int = 64, ctx: Optional[Context] = None,
+                            stream: Optional[torch.cuda.Stream] = None):
+    """dagpu_blob_commitments_device: inclusion.CreateCommitment of many share
+    ranges of squares resident in HBM, compared with `expected` on the device.
+
+    blobs: (nblobs, 3) int64-like on the HOST, {square, first_share,
+    share_count}; squares: a contiguous cuda uint8 tensor holding n squares,
+    square i at byte i * square_stride, rows row_pitch bytes apart (n is what
+    the tensor holds at that stride); expected: (nblobs, 32) uint8, a cuda
+    tensor or a host array (uploaded on `stream`), or None.  Returns
+    (commitments (nblobs, 32) uint8, status (nblobs,) int32, square_status (n,)
+    int32) as cuda tensors; status bits _abi.COMMIT_MISMATCH /
+    COMMIT_PUSH_ORDER, square_status the OR over each square's blobs.  Enqueued
+    on `stream`: it does not synchronise."""
+    import numpy as np
+    c = ctx or default_context()
+    rec = np.ascontiguousarray(np.asarray(blobs, dtype=np.int64).reshape(-1, 3))
+    nb, dev = int(rec.shape[0]), squares.device
+    if squares.dtype != torch.uint8 or not squares.is_contiguous():
+        raise ValueError("squares must be a contiguous cuda uint8 tensor")
+    one = (k - 1) * row_pitch + k * 512
+    n = 0 if squares.numel() < one else 1 + (squares.numel() - one) // square_stride if square_stride else 1
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    need = c._L.dagpu_blob_commitments_workspace_size(k, nb, int(rec[:, 2].clip(min=0).sum()))
+    with torch.cuda.stream(s):
+        if expected is not None and not isinstance(expected, torch.Tensor):
+            host = np.array(expected, dtype=np.uint8).reshape(-1)  # a writable copy for torch
+            expected = torch.from_numpy(host).pin_memory().to(dev, non_blocking=True)
+        out = torch.empty((nb, 32), dtype=torch.uint8, device=dev)
+        status = torch.empty((nb,), dtype=torch.int32, device=dev)
+        sq_status = torch.empty((n,), dtype=torch.int32, device=dev)
+        ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
+    if expected is not None and (expected.dtype != torch.uint8 or expected.device != dev
+                                 or not expected.is_contiguous() or expected.numel() != nb * 32):
+        raise ValueError("expected must hold 32 bytes per blob, contiguous uint8 on the squares' device")
+    rc = c._L.dagpu_blob_commitments_device(
+        c.handle, k, n, nb, _abi.addr(rec), _abi.addr(squares), square_stride, row_pitch, threshold, _abi.addr(out),
+        _abi.addr(expected) if expected is not None and nb else None, _abi.addr(status),
+        _abi.addr(sq_status) if n else None, _abi.addr(ws), _stream_handle(s))
+    if rc != 0:
+        raise DAError(rc, c.last_error())
+    return out, status, sq_status
+
+
 class DeviceSquares:
     """n squares of width k resident on one GPU.
 
@@ -325,6 +370,10 @@ class DeviceSquares:
         # tensors of started repairs, held until their join (dagpu_repair_start:
         # the buffers must stay valid until the joined stream has passed the repair)
         self._held = {}
+        # load_txs: each block's plan and the length of its packed txs, for
+        # blob_table / check_commitments
+        self._plans = None
+        self._src_lens = None
 
     def q0(self) -> torch.Tensor:
         """(n, k, k*512) view of Q0 inside the EDS buffer."""
@@ -379,6 +428,43 @@ class DeviceSquares:
                               else (self.ods, self.k * self.k * 512, self.k * 512))
         write_squares_device(self.k, [p for _, p, _ in planned], [b for _, _, b in planned], out.view(-1), stride,
                              pitch, ctx=self.ctx, stream=stream)
+        self._plans = [p for _, p, _ in planned]
+        self._src_lens = [int(b.size) for _, _, b in planned]
+
+    def blob_table(self):
+        """Every blob of the batch load_txs wrote, block by block in plan order:
+        (records, keys), records the (nblobs, 3) int64 {square, first_share,
+        share_count} that blob_commitments_device takes, keys the (nblobs, 2)
+        int64 {block, data_off}, data_off the offset of the blob's data in the
+        block's packed txs (square.plan_blobs)."""
+        import numpy as np
+
+        from . import square as sq
+        if self._plans is None:
+            raise ValueError("no plans: blob_table follows load_txs")
+        rec, key = [], []
+        for i, p in enumerate(self._plans):
+            t = sq.plan_blobs(p).astype(np.int64)
+            rec.append(np.stack([np.full(len(t), i, np.int64), t[:, 0], t[:, 1]], axis=1))
+            key.append(np.stack([np.full(len(t), i, np.int64), t[:, 2]], axis=1))
+        return np.concatenate(rec).reshape(-1, 3), np.concatenate(key).reshape(-1, 2)
+
+    def check_commitments(self, expected=None, stream: Optional[torch.cuda.Stream] = None,
+                          threshold: Optional[int] = None):
+        """The share commitment of every blob of the batch from the squares
+        load_txs wrote (the ODS, or Q0 of the EDS when in_place: before or after
+        extend(), which never changes Q0), compared on the device with
+        `expected` ((nblobs, 32), in blob_table order) when given.  Returns
+        blob_commitments_device's (commitments, status, square_status), enqueued
+        on `stream`: one read of square_status tells which blocks to reject."""
+        from . import square as sq
+        rec, _ = self.blob_table()
+        w = 2 * self.k
+        buf, stride, pitch = ((self.eds, w * w * 512, w * 512) if self.in_place
+                              else (self.ods, self.k * self.k * 512, self.k * 512))
+        return blob_commitments_device(self.k, rec, buf.view(-1), stride, pitch, expected=expected,
+                                       threshold=sq.SUBTREE_ROOT_THRESHOLD if threshold is None else threshold,
+                                       ctx=self.ctx, stream=stream)
 
     def _ck(self, rc: int) -> None:
         if rc != 0:

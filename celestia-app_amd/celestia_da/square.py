@@ -442,6 +442,66 @@ def plan_native(txs: Sequence[bytes], max_square_size: int = SQUARE_SIZE_UPPER_B
     return k, plan, normal + blob
 
 
+def plan_blobs(plan):
+    """dagpu_square_plan_blobs: the blob table of a plan as an (nblob, 4) uint32
+    array {first_share, share_count, data_off, data_len} in plan order
+    (ascending first_share).  data_off is the offset of the blob's data in the
+    block's packed txs.  Raises ValueError for a plan the check refuses."""
+    import ctypes
+
+    import numpy as np
+
+    from . import _abi
+    L = _abi.lib()
+    plan = np.ascontiguousarray(plan, dtype=np.uint8)
+    n = ctypes.c_size_t(0)
+    rc = L.dagpu_square_plan_blobs(_abi.addr(plan), plan.size, None, 0, ctypes.byref(n))
+    out = np.zeros((n.value, 4), np.uint32)
+    if n.value:
+        rc = L.dagpu_square_plan_blobs(_abi.addr(plan), plan.size, _abi.addr(out), n.value, ctypes.byref(n))
+    if rc != 0:
+        raise ValueError(f"dagpu_square_plan_blobs: status {rc}: {L.dagpu_last_error(None).decode()}")
+    return out
+
+
+def expected_commitments(txs: Sequence[bytes], plan):
+    """The share commitments the block's PFBs declare, as an (nblob, 32) uint8
+    array in plan order: each BlobTx's MsgPayForBlobs is decoded
+    (blobtx.pfb_of_tx) and its blobs are tied to the plan's through the offset
+    of their data in the packed txs.  Raises ShareError when a PFB's counts
+    disagree with its blobs (ErrBlobSizeMismatch, ErrInvalidShareCommitments of
+    x/blob/types/blob_tx.go) or a plan blob matches no blob of the txs."""
+    import numpy as np
+    declared = {}
+    at = 0
+    for raw in txs:
+        raw = bytes(raw)
+        t, ok = btx.unmarshal_blob_tx(raw)
+        if ok:
+            pfb = btx.pfb_of_tx(t.tx)
+            if len(pfb.blob_sizes) != len(t.blobs):
+                raise ShareError(f"ErrBlobSizeMismatch: actual {len(t.blobs)} declared {len(pfb.blob_sizes)}")
+            if len(pfb.share_commitments) != len(t.blobs):
+                raise ShareError(f"ErrInvalidShareCommitments: {len(pfb.share_commitments)} commitments for "
+                                 f"{len(t.blobs)} blobs")
+            for j, (off, ln) in enumerate(btx.blob_data_offsets(raw)):
+                if pfb.blob_sizes[j] != ln:
+                    raise ShareError(f"ErrBlobSizeMismatch: actual {ln} declared {pfb.blob_sizes[j]}")
+                if len(pfb.share_commitments[j]) != 32:
+                    raise ShareError(f"ErrInvalidShareCommitments: commitment {j} has "
+                                     f"{len(pfb.share_commitments[j])} bytes")
+                declared[at + off] = pfb.share_commitments[j]
+        at += len(raw)
+    table = plan_blobs(plan)
+    out = np.zeros((len(table), 32), np.uint8)
+    for i, row in enumerate(table):
+        c = declared.get(int(row[2]))
+        if c is None:
+            raise ShareError(f"plan blob {i} (data at {int(row[2])}) is no blob of these txs")
+        out[i] = np.frombuffer(c, np.uint8)
+    return out
+
+
 def write_plan_host(plan, txs: Sequence[bytes], k: int, row_pitch: Optional[int] = None, out=None):
     """dagpu_square_plan_write_host: the ODS of a plan and its txs, computed
     share by share with the function the kernel runs.  Returns `out` (a uint8

@@ -482,6 +482,7 @@ void dagpu_destroy(dagpu_ctx* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
   c->h_out.release();
+  c->commit_stage.release();
   c->res.release();
   c->ods.release(); c->eds.release(); c->rr.release(); c->cr.release();
   c->dah.release(); c->status.release(); c->ws.release();

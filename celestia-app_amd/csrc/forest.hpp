@@ -98,6 +98,32 @@ hipError_t launch_prove_emit(const ProveArgs& a, hipStream_t s);
 hipError_t launch_prove_namespaces(const ProveArgs& a, hipStream_t s);
 hipError_t launch_prove_shares(const ProveArgs& a, hipStream_t s);
 
+// Share commitments from squares resident in HBM (blob_commit.hip).  Every
+// table was checked and laid out on the host (commit_layout.hpp); the kernels
+// check nothing.
+struct CommitArgs {
+  const uint32_t* blob;       // nblobs x {square, first_share}
+  const uint32_t* share_pre;  // nblobs + 1 prefix sums of share counts
+  const uint32_t* sub_pre;    // nblobs + 1 prefix sums of subtree counts
+  const uint32_t* sub;        // nsub x {blob, first leaf record, size}
+  const uint32_t* work;       // nwork indexes of the subtrees of size >= 2
+  uint32_t nblobs, nshares, nsub, nwork;
+  uint32_t log2k;
+  const uint8_t* squares;  // square i at squares + i * square_stride, rows row_pitch apart
+  uint64_t square_stride, row_pitch;
+  uint8_t* leaves;       // nshares 96-B records; even tree levels reuse them
+  uint8_t* inner;        // nshares / 2 + 1 records: the odd tree levels
+  uint8_t* dig0;         // nsub 32-B digests: RFC-6962 leaf level, then every second level
+  uint8_t* dig1;         // the levels between
+  uint8_t* commitments;  // nblobs x 32 B
+  const uint8_t* expected;  // nblobs x 32 B or null
+  int32_t* status;          // nblobs, zeroed before the subtree kernel
+  int32_t* square_status;   // per square or null, zeroed before the commit kernel
+};
+hipError_t launch_commit_leaves(const CommitArgs& a, hipStream_t s);
+hipError_t launch_commit_subtrees(const CommitArgs& a, hipStream_t s);
+hipError_t launch_commit_roots(const CommitArgs& a, hipStream_t s);
+
 // Namespace search over the row trees of one square (nmt_namespace.hip;
 // arithmetic in ns_find.hpp).  One lane per (query, row).
 struct NsFindArgs {

@@ -104,6 +104,11 @@ struct dagpu_ctx {
   std::vector<void*> mailboxes;
   hipEvent_t ev_loaded[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr};
   HostBuf h_out;
+  // commitments from resident squares (commit_host.cpp): page-locked staging of
+  // the call's tables, held under commit_mu from the fill until the upload has
+  // left it
+  std::mutex commit_mu;
+  HostBuf commit_stage;
   // generic forests / commitments / split square (trees.cpp, split.cpp)
   DevBuf t_leaf_data, t_leaves, t_inner, t_meta, t_out, t_status, t_flags;
   // profiling: per-kernel brackets (prof) and, for host-path calls, a stage

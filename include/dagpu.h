@@ -728,6 +728,70 @@ int dagpu_square_write_device(dagpu_ctx* ctx, uint32_t k, size_t n, const uint8_
                               size_t src_bytes, uint8_t* d_ods, size_t square_stride, size_t row_pitch,
                               void* d_workspace, void* stream);
 
+/* ---- Share commitments from squares resident in HBM ----------------------
+ * ProcessProposal recomputes every blob's share commitment and compares it
+ * with the one its MsgPayForBlobs declares (x/blob/types/blob_tx.go:91-100,
+ * called at app/process_proposal.go:120) before it builds the square.  With
+ * the squares written in HBM (dagpu_square_write_device) the commitments of
+ * every blob of every block of a batch come from those bytes in one enqueue:
+ * inclusion.CreateCommitment (pkg/inclusion/commitment.go:19-75) depends on
+ * the blob's shares alone.
+ *
+ * dagpu_square_plan_blobs: the blob table of a plan, 4 uint32 per blob
+ * {first_share, share_count, data_off, data_len} in plan order (ascending
+ * first_share; the plan sorts blobs by namespace, so this is not tx order).
+ * data_off is the offset of the blob's data in the block's packed txs: a
+ * caller that parsed the BlobTxs ties a plan blob back to (tx, blob index)
+ * with it, and so to the commitment the PFB declares.  Runs
+ * dagpu_square_plan_check first (DAGPU_ERR_ARG, message dagpu_last_error(NULL));
+ * needs no context and no device.  *nblob is set even when cap (in blobs) is
+ * too small, which returns DAGPU_ERR_ARG.
+ *
+ * dagpu_blob_commitments_device: n squares of width k addressed as in
+ * dagpu_square_write_device (square i at d_squares + i * square_stride, rows
+ * row_pitch apart: the packed ODS batch or Q0 inside an EDS batch), and nblobs
+ * HOST records of three int64 {square, first_share, share_count}: blob b is
+ * shares [first, first + count) of that square in row-major order over the
+ * k x k ODS.  For each, with w = SubTreeWidth(count, subtree_root_threshold)
+ * (blob_share_commitment_rules.go:85-101) and the split of
+ * MerkleMountainRangeSizes(count, w) (commitment.go:85-107): the nmt root of
+ * each subtree, leaf j = 0x00 | share[0:29] | share (namespace | share for a
+ * range that is one blob, commitment.go:53-63), nodes by nmt HashNode with
+ * IgnoreMaxNamespace; then merkle.HashFromByteSlices of the 90-B roots
+ * (commitment.go:73) into d_commitments[b*32..].
+ * d_status[b] (int32): 0, or the OR of
+ *   DAGPU_COMMIT_MISMATCH    d_expected != NULL and the 32 bytes differ from
+ *                            d_expected[b*32..] (the comparison of
+ *                            blob_tx.go:96-99)
+ *   DAGPU_COMMIT_PUSH_ORDER  inside some subtree a leaf's namespace is below
+ *                            its predecessor's (nmt ErrInvalidPushOrder); the
+ *                            commitment bytes of such a blob are unspecified.
+ *                            Ranges of <= threshold shares have one-leaf
+ *                            subtrees and never set it, as in nmt.
+ * d_square_status (n int32, may be NULL) is zeroed on the stream and receives
+ * the OR of the statuses of each square's blobs: one read of n words tells
+ * which blocks to reject.
+ * Checked on the host before anything is enqueued: k a power of two (<= 1024,
+ * else DAGPU_ERR_UNSUPPORTED), threshold > 0, row_pitch >= k*512, d_squares,
+ * square_stride and row_pitch multiples of 16, and for every record
+ * 0 <= square < n, count >= 1, 0 <= first, first + count <= k*k; a refusal
+ * returns DAGPU_ERR_ARG and its message names the blob.  nblobs == 0 is valid
+ * and only zeroes d_square_status.
+ * d_workspace (16-B aligned, dagpu_blob_commitments_workspace_size(k, nblobs,
+ * sum of share counts) bytes) must stay valid until the kernels have run; the
+ * call returns once the tables have left host memory, with three kernels
+ * enqueued on `stream`.  With NULL the library allocates it and waits. */
+#define DAGPU_COMMIT_MISMATCH 1
+#define DAGPU_COMMIT_PUSH_ORDER 2
+size_t dagpu_blob_commitments_workspace_size(uint32_t k, size_t nblobs, size_t nshares_total);
+int dagpu_blob_commitments_device(dagpu_ctx* ctx, uint32_t k, size_t n, size_t nblobs,
+                                  const int64_t* blobs /* HOST, 3 per blob */, const uint8_t* d_squares,
+                                  size_t square_stride, size_t row_pitch, uint32_t subtree_root_threshold,
+                                  uint8_t* d_commitments, const uint8_t* d_expected /* may be NULL */,
+                                  int32_t* d_status, int32_t* d_square_status /* may be NULL */,
+                                  void* d_workspace, void* stream);
+int dagpu_square_plan_blobs(const uint8_t* plan, size_t plan_bytes, uint32_t* out, size_t cap, size_t* nblob);
+
 #ifdef __cplusplus
 }
 #endif
