@@ -76,6 +76,12 @@ EXPORTS = (
     "dagpu_blob_commitments_workspace_size",
     "dagpu_blob_commitments_device",
     "dagpu_square_plan_blobs",
+    "dagpu_square_scan_workspace_size",
+    "dagpu_square_scan_device",
+    "dagpu_square_scan_host",
+    "dagpu_square_read_workspace_size",
+    "dagpu_square_read_device",
+    "dagpu_compact_units",
     "dagpu_profile_enable",
     "dagpu_profile_read",
     "dagpu_profile_stages",
@@ -112,6 +118,13 @@ EXPORTS = (
 # d_status bits of dagpu_blob_commitments_device
 COMMIT_MISMATCH = 1
 COMMIT_PUSH_ORDER = 2
+
+# dagpu_square_scan_device / dagpu_square_read_device (include/dagpu.h)
+SCAN_OK, SCAN_NAMESPACE, SCAN_INCONSISTENT, SCAN_LENGTH, SCAN_OVERFLOW = 0, 1, 2, 3, 4
+SCAN_SUMMARY_WORDS = 8
+SEQ_SPARSE, SEQ_TX, SEQ_PFB, SEQ_PADDING, SEQ_VERSION_SHIFT = 1, 2, 4, 8, 8
+SEQ_RECORD_BYTES = 64
+READ_BLOBS, READ_COMPACT = 1, 2
 
 PROVE_REQ_WORDS = 4
 NMT_DESC_WORDS = 8
@@ -232,6 +245,16 @@ def lib() -> ctypes.CDLL:
         L.dagpu_blob_commitments_device.argtypes = [vp, ctypes.c_uint32, sz, sz, vp, vp, sz, sz, ctypes.c_uint32, vp, vp,
                                                     vp, vp, vp, vp]
         L.dagpu_square_plan_blobs.argtypes = [vp, sz, vp, sz, ctypes.POINTER(sz)]
+        u32 = ctypes.c_uint32
+        L.dagpu_square_scan_workspace_size.argtypes = [u32, sz]
+        L.dagpu_square_scan_workspace_size.restype = sz
+        L.dagpu_square_scan_device.argtypes = [vp, u32, sz, vp, sz, sz, u32, vp, vp, vp, vp, vp]
+        L.dagpu_square_scan_host.argtypes = [u32, sz, vp, sz, sz, u32, vp, vp]
+        L.dagpu_square_read_workspace_size.argtypes = [u32, sz, u32, sz]
+        L.dagpu_square_read_workspace_size.restype = sz
+        L.dagpu_square_read_device.argtypes = [vp, u32, sz, vp, sz, sz, u32, vp, vp, vp, sz, u32, vp, vp, vp, vp, sz,
+                                               vp, vp]
+        L.dagpu_compact_units.argtypes = [vp, sz, u32, vp, vp, sz, ctypes.POINTER(sz)]
         L.dagpu_repair_batch_device_ex.argtypes = [vp, ctypes.c_uint32, sz, vp, vp, vp, vp, vp, vp,
                                                    vp, vp]
         L.dagpu_repair_start.argtypes = [vp, ctypes.c_uint32, sz, vp, vp, vp, vp, vp, vp, vp,

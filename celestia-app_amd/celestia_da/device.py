@@ -342,6 +342,87 @@ def blob_commitments_device(k: int, blobs, squares: torch.Tensor, square_stride:
     return out, status, sq_status
 
 
+def _squares_held(k: int, squares: torch.Tensor, square_stride: int, row_pitch: int) -> int:
+    """How many squares a contiguous uint8 tensor holds at these strides."""
+    if squares.dtype != torch.uint8 or not squares.is_contiguous():
+        raise ValueError("squares must be a contiguous cuda uint8 tensor")
+    one = (k - 1) * row_pitch + k * 512
+    return 0 if squares.numel() < one else 1 + (squares.numel() - one) // square_stride if square_stride else 1
+
+
+def scan_squares_device(k: int, squares: torch.Tensor, square_stride: int, row_pitch: int,
+                        seq_cap: Optional[int] = None, ctx: Optional[Context] = None,
+                        stream: Optional[torch.cuda.Stream] = None, summary_host: bool = True):
+    """dagpu_square_scan_device: shares.ParseShares of the squares a cuda uint8
+    tensor holds (square i at byte i * square_stride, rows row_pitch apart).
+    Returns (records, summary, host): records an (n, seq_cap, 64) uint8 cuda
+    tensor of dagpu_seq_record (square.seq_dtype()), seq_cap = k*k by default;
+    summary (n, 8) int32 on the device; host its copy as a numpy array, for
+    which the call waits, or None with summary_host=False, when everything is
+    only enqueued on `stream`.  Records past a square's sequence count keep
+    what torch.empty left there."""
+    import numpy as np
+    c = ctx or default_context()
+    n, dev = _squares_held(k, squares, square_stride, row_pitch), squares.device
+    cap = k * k if seq_cap is None else int(seq_cap)
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.stream(s):
+        records = torch.empty((n, cap, _abi.SEQ_RECORD_BYTES), dtype=torch.uint8, device=dev)
+        summary = torch.empty((n, _abi.SCAN_SUMMARY_WORDS), dtype=torch.int32, device=dev)
+        ws = torch.empty((max(c._L.dagpu_square_scan_workspace_size(k, n), 16),), dtype=torch.uint8, device=dev)
+    host = np.zeros((n, _abi.SCAN_SUMMARY_WORDS), np.int32) if summary_host else None
+    rc = c._L.dagpu_square_scan_device(c.handle, k, n, _abi.addr(squares), square_stride, row_pitch, cap,
+                                       _abi.addr(records), _abi.addr(summary), _abi.addr(host), _abi.addr(ws),
+                                       _stream_handle(s))
+    if rc != 0:
+        raise DAError(rc, c.last_error())
+    return records, summary, host
+
+
+def read_sequences_device(k: int, squares: torch.Tensor, square_stride: int, row_pitch: int, records: torch.Tensor,
+                          summary: torch.Tensor, payload_cap: int, namespaces=None,
+                          classes: int = _abi.READ_BLOBS | _abi.READ_COMPACT, ctx: Optional[Context] = None,
+                          stream: Optional[torch.cuda.Stream] = None, payload: Optional[torch.Tensor] = None):
+    """dagpu_square_read_device over a scan's records and summary (both on the
+    device): the payload of the non-padding sequences of the classes in
+    `classes` (_abi.READ_BLOBS, READ_COMPACT) and of `namespaces` (29-byte
+    values on the host; None: all), gathered into a cuda uint8 tensor of
+    payload_cap bytes (`payload`, when given, is written in place).  Returns
+    (selected (n*seq_cap,) int32 indices into the record table (the uint32 the
+    library writes), offsets (n*seq_cap,) int64, totals (3,) int64 {n_selected,
+    payload_bytes, overflow}, payload), all on the device and only enqueued on
+    `stream`; entries past n_selected are not written."""
+    import numpy as np
+    c = ctx or default_context()
+    n, dev = _squares_held(k, squares, square_stride, row_pitch), squares.device
+    if records.dim() != 3 or records.shape[0] != n or records.shape[2] != _abi.SEQ_RECORD_BYTES \
+            or not records.is_contiguous() or records.dtype != torch.uint8:
+        raise ValueError("records must be the (n, seq_cap, 64) uint8 tensor of scan_squares_device")
+    cap = int(records.shape[1])
+    ns = None
+    if namespaces is not None:
+        ns = np.frombuffer(b"".join(bytes(x) for x in namespaces), np.uint8).copy()
+        if ns.size != 29 * len(namespaces):
+            raise ValueError("namespaces are 29 bytes each")
+    n_ns = 0 if ns is None else len(namespaces)
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.stream(s):
+        selected = torch.empty((n * cap,), dtype=torch.int32, device=dev)
+        offsets = torch.empty((n * cap,), dtype=torch.int64, device=dev)
+        totals = torch.empty((3,), dtype=torch.int64, device=dev)
+        if payload is None:
+            payload = torch.empty((max(int(payload_cap), 16),), dtype=torch.uint8, device=dev)
+        ws = torch.empty((max(c._L.dagpu_square_read_workspace_size(k, n, cap, n_ns), 16),), dtype=torch.uint8,
+                         device=dev)
+    rc = c._L.dagpu_square_read_device(c.handle, k, n, _abi.addr(squares), square_stride, row_pitch, cap,
+                                       _abi.addr(records), _abi.addr(summary), _abi.addr(ns) if n_ns else None, n_ns,
+                                       classes, _abi.addr(selected), _abi.addr(offsets), _abi.addr(totals),
+                                       _abi.addr(payload), int(payload_cap), _abi.addr(ws), _stream_handle(s))
+    if rc != 0:
+        raise DAError(rc, c.last_error())
+    return selected, offsets, totals, payload
+
+
 class DeviceSquares:
     """n squares of width k resident on one GPU.
 
@@ -374,6 +455,8 @@ class DeviceSquares:
         # blob_table / check_commitments
         self._plans = None
         self._src_lens = None
+        # scan(): (records, summary, host summary, (buffer, square_stride, row_pitch))
+        self._scan = None
 
     def q0(self) -> torch.Tensor:
         """(n, k, k*512) view of Q0 inside the EDS buffer."""
@@ -465,6 +548,119 @@ class DeviceSquares:
         return blob_commitments_device(self.k, rec, buf.view(-1), stride, pitch, expected=expected,
                                        threshold=sq.SUBTREE_ROOT_THRESHOLD if threshold is None else threshold,
                                        ctx=self.ctx, stream=stream)
+
+    # ---- square read (dagpu_square_scan_device / dagpu_square_read_device) ----
+
+    def _resident(self, from_eds: Optional[bool] = None):
+        """(buffer, square_stride, row_pitch) of the squares: Q0 of the EDS when
+        in_place, when there is no ODS buffer or when from_eds is set (after a
+        repair the content is there), else the ODS batch."""
+        w = 2 * self.k
+        if self.in_place or self.ods is None or from_eds:
+            return self.eds.view(-1), w * w * 512, w * 512
+        return self.ods.view(-1), self.k * self.k * 512, self.k * 512
+
+    def _fetch(self, i: int, where):
+        """fetch(first, end) -> List[Share] of square i, downloaded row by row."""
+        from .shares import Share
+        buf, stride, pitch = where
+        k = self.k
+
+        def fetch(a, b):
+            b = min(b, k * k)
+            if a >= b:
+                return []
+            r0, r1 = a // k, (b - 1) // k
+            rows = [buf[i * stride + r * pitch:i * stride + r * pitch + k * 512].cpu().numpy().tobytes()
+                    for r in range(r0, r1 + 1)]
+            flat = b"".join(rows)
+            return [Share(flat[(s - r0 * k) * 512:(s - r0 * k + 1) * 512]) for s in range(a, b)]
+        return fetch
+
+    def scan(self, stream: Optional[torch.cuda.Stream] = None, from_eds: Optional[bool] = None,
+             seq_cap: Optional[int] = None, check: bool = True):
+        """shares.ParseShares of every square where it lies (dagpu_square_scan_device);
+        the records and summary stay on the device (self._scan).  Returns the (n, 8) int32 summary on the host.  With
+        check, a square the reference refuses raises ShareError with the
+        mirror's message: the mirror runs on the offending share or sequence
+        alone, downloaded."""
+        import numpy as np
+
+        from . import square as sq
+        where = self._resident(from_eds)
+        records, summary, host = scan_squares_device(self.k, where[0], where[1], where[2], seq_cap=seq_cap,
+                                                     ctx=self.ctx, stream=stream)
+        records, summary, host = records[:self.n], summary[:self.n], host[:self.n]
+        self._scan = (records, summary, host, where)
+        if check:
+            for i in range(self.n):
+                if host[i, 0] != _abi.SCAN_OK:
+                    cap = int(records.shape[1])
+                    rec = records[i, :min(int(host[i, 3]), cap)].cpu().numpy().view(sq.seq_dtype()).reshape(-1)
+                    sq.raise_scan_error(host[i], np.ascontiguousarray(rec), self._fetch(i, where))
+        return host
+
+    def _parsed(self, classes: int, namespaces=None, stream: Optional[torch.cuda.Stream] = None,
+                from_eds: Optional[bool] = None):
+        """One square.ParsedSquare per square over a fresh scan: the payload of
+        the sequences of `classes` / `namespaces` gathered in HBM and
+        downloaded, nothing else.  A square the reference refuses raises when
+        its ParsedSquare is asked for content."""
+        import numpy as np
+
+        from . import square as sq
+        self.scan(stream=stream, from_eds=from_eds, check=False)
+        records, summary, host, where = self._scan
+        ok = host[:, 0] == _abi.SCAN_OK
+        need = 0
+        if classes & _abi.READ_BLOBS:
+            need += int(host[ok, 5].astype(np.int64).sum())
+        if classes & _abi.READ_COMPACT:
+            need += int(host[ok, 6].astype(np.int64).sum())
+        cap = int(records.shape[1])
+        selected, offsets, totals, payload = read_sequences_device(
+            self.k, where[0], where[1], where[2], records, summary, need, namespaces=namespaces, classes=classes,
+            ctx=self.ctx, stream=stream)
+        s = stream if stream is not None else torch.cuda.current_stream(self.eds.device)
+        with torch.cuda.stream(s):
+            nsel, nbytes, over = (int(v) for v in totals.cpu())
+            assert not over, "the payload buffer was sized from the summary"
+            slots = selected[:nsel].cpu().numpy().astype(np.int64) & 0xFFFFFFFF
+            offs = offsets[:nsel].cpu().numpy()
+            data = payload[:nbytes].cpu().numpy()
+            top = max(1, int(host[:, 3].clip(max=cap).max()))
+            rec = np.ascontiguousarray(records[:, :top].cpu().numpy()).view(sq.seq_dtype()).reshape(self.n, top)
+        at = {int(slot): int(off) for slot, off in zip(slots, offs)}
+        out = []
+        for i in range(self.n):
+            r = rec[i, :min(int(host[i, 3]), cap)]
+
+            def get(j, i=i, r=r):
+                o = at[i * cap + j]
+                return data[o:o + int(r["payload"][j])].tobytes()
+            out.append(sq.ParsedSquare(self.k, r, host[i], get, self._fetch(i, where)))
+        return out
+
+    def read_blobs(self, namespaces=None, stream: Optional[torch.cuda.Stream] = None,
+                   from_eds: Optional[bool] = None):
+        """Every square's blobs (of `namespaces`, 29-byte values; all by
+        default) as shares.parse_blobs returns them: a List[Blob] per square.
+        Only the blobs' bytes cross PCIe."""
+        return [p.blobs(namespaces) for p in self._parsed(_abi.READ_BLOBS, namespaces, stream, from_eds)]
+
+    def read_txs(self, stream: Optional[torch.cuda.Stream] = None, from_eds: Optional[bool] = None):
+        """Per square (txs, wrapped PFBs): shares.parse_txs of the tx namespace's
+        and of the PFB namespace's shares."""
+        return [(p.txs(), p.wrapped_pfbs()) for p in self._parsed(_abi.READ_COMPACT, None, stream, from_eds)]
+
+    def deconstruct(self, pfb_blob_sizes, stream: Optional[torch.cuda.Stream] = None,
+                    from_eds: Optional[bool] = None):
+        """square.Deconstruct of every square: the List of its txs, BlobTxs
+        re-assembled (square.ParsedSquare.deconstruct over the gathered payload;
+        pfb_blob_sizes(tx) -> the blob sizes of a PFB, as square.deconstruct
+        takes it)."""
+        return [p.deconstruct(pfb_blob_sizes)
+                for p in self._parsed(_abi.READ_BLOBS | _abi.READ_COMPACT, None, stream, from_eds)]
 
     def _ck(self, rc: int) -> None:
         if rc != 0:

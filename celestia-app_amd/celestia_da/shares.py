@@ -18,9 +18,14 @@ mirror of pkg/shares and the namespace constants it uses:
                                             pkg/shares/info_byte.go, reserved_bytes.go, utils.go
   namespace constants / validation          pkg/namespace/consts.go, namespace.go
 
-This is byte bookkeeping that produces the ODS the GPU path extends (and
-parses squares the GPU path repaired); it is control-heavy and stays on the
-host, as SURVEY.md §8(f)-4 plans.  Namespaces are 29-byte `bytes`
+This is the byte bookkeeping of a square, control-heavy and on the host, as
+SURVEY.md §8(f)-4 plans; it is the specification of the two native routes.
+Squares are written in HBM from raw txs by dagpu_square_write_device
+(square.construct_device, DeviceSquares.load_txs), and squares resident in HBM
+(written there, loaded, or repaired) are parsed where they lie by
+dagpu_square_scan_device / dagpu_square_read_device (DeviceSquares.scan,
+read_blobs, read_txs, deconstruct; square.parse_native on the host), which
+re-raise this module's messages.  Namespaces are 29-byte `bytes`
 (version || 28-byte ID); shares are 512-byte `bytes` wrapped in `Share`.
 """
 from __future__ import annotations

@@ -547,3 +547,246 @@ def blob_share_range(txs: Sequence[bytes], tx_index: int, blob_index: int,
     b = Builder(square_size_upper_bound(app_version), app_version, *txs)
     start = b.find_blob_starting_index(tx_index, blob_index)
     return Range(start, start + b.blob_share_length(tx_index, blob_index))
+
+
+# ---- square read: sequences, blobs and tx streams back out of a square ------------------
+# (csrc/square_read.hpp; dagpu_square_scan_host / dagpu_square_scan_device,
+# dagpu_square_read_device, dagpu_compact_units).  The scan is shares.ParseShares,
+# the units are parseRawData; the checks of Deconstruct are made on the records.
+
+def seq_dtype():
+    """numpy dtype of dagpu_seq_record (64 B)."""
+    import numpy as np
+    return np.dtype([("ns", "u1", 32), ("first", "<u4"), ("count", "<u4"), ("seq_len", "<u4"), ("flags", "<u4"),
+                     ("reserved", "<u4"), ("payload", "<u4"), ("pad", "<u4", 2)])
+
+
+def raise_scan_error(summary, records, fetch) -> None:
+    """Raise what the mirror raises for a scan summary whose code is not OK:
+    the mirror runs on the offending share or sequence alone, which
+    fetch(first, end) -> List[Share] hands over (downloaded when the square is
+    on the device).  Returns when the code is OK."""
+    from . import _abi
+    code, index = int(summary[0]), int(summary[1])
+    if code == _abi.SCAN_OK:
+        return
+    if code == _abi.SCAN_OVERFLOW:
+        raise ShareError(f"square has {index} share sequences, the record table holds {len(records)}")
+    if code in (_abi.SCAN_NAMESPACE, _abi.SCAN_INCONSISTENT):
+        sh.parse_shares(fetch(index, index + 1), False)
+    else:
+        at = int(records["first"].searchsorted(index))
+        count = int(records["count"][at]) if at < len(records) and records["first"][at] == index else 1
+        sh.parse_shares(fetch(index, index + count), False)
+    raise ShareError(f"scan code {code} at share {index}, which the mirror accepts")
+
+
+def compact_units(stream, reserved: int) -> List[bytes]:
+    """dagpu_compact_units: the units of a compact sequence's payload, from its
+    first share's reserved bytes on (shares.parse_txs of the sequence's shares)."""
+    import ctypes
+
+    import numpy as np
+
+    from . import _abi
+    L = _abi.lib()
+    buf = np.frombuffer(stream, np.uint8) if not hasattr(stream, "ctypes") else np.ascontiguousarray(stream, np.uint8)
+    cap = max(1, buf.size // 2)  # a unit takes two bytes at least, but for the last
+    off, ln = np.empty(cap + 1, np.uint64), np.empty(cap + 1, np.uint64)
+    n = ctypes.c_size_t(0)
+    rc = L.dagpu_compact_units(_abi.addr(buf) if buf.size else None, buf.size, reserved, _abi.addr(off),
+                               _abi.addr(ln), cap + 1, ctypes.byref(n))
+    if rc != 0:
+        msg = L.dagpu_last_error(None).decode()
+        raise ShareError(msg) if rc == _abi.ERR_SQUARE else ValueError(f"dagpu_compact_units: status {rc}: {msg}")
+    raw = buf.tobytes()
+    return [raw[int(off[i]):int(off[i]) + int(ln[i])] for i in range(n.value)]
+
+
+class ParsedSquare:
+    """One scanned square: its sequence records (a structured array of
+    seq_dtype(), in share order), its 8-word summary, and two callables that
+    reach its bytes: payload(j) -> bytes of record j's payload, and
+    fetch(first, end) -> List[Share].  Made by parse_native (host executor) and
+    by DeviceSquares (the payloads gathered in HBM)."""
+
+    def __init__(self, k: int, records, summary, payload, fetch):
+        self.k, self.records, self.summary = int(k), records, summary
+        self._payload, self._fetch = payload, fetch
+
+    def check(self) -> None:
+        raise_scan_error(self.summary, self.records, self._fetch)
+
+    def sequences(self, flag: int):
+        """Indices of the non-padding records with class flag `flag`."""
+        from . import _abi
+        f = self.records["flags"]
+        return [int(j) for j in ((f & flag != 0) & (f & _abi.SEQ_PADDING == 0)).nonzero()[0]]
+
+    def _all_shares(self):
+        """The host route of a square with a share of another version, which
+        parse_blobs / parse_txs refuse only inside the range they are given."""
+        return self._fetch(0, self.k * self.k) if int(self.summary[2]) >= 0 else None
+
+    def blobs(self, namespaces=None) -> List[Blob]:
+        """shares.parse_blobs of the square's sparse shares (of the namespaces
+        given, all by default)."""
+        from . import _abi
+        self.check()
+        want = None if namespaces is None else {bytes(n) for n in namespaces}
+        shares = self._all_shares()
+        if shares is not None:
+            return [b for b in sh.parse_blobs([s for s in shares if not s.is_compact_share()])
+                    if want is None or b.namespace() in want]
+        out = []
+        for j in self.sequences(_abi.SEQ_SPARSE):
+            ns = self.records["ns"][j][:sh.NAMESPACE_SIZE].tobytes()
+            if want is None or ns in want:
+                out.append(Blob.new(ns, self._payload(j), 0))
+        return out
+
+    def _units(self, flag: int) -> List[bytes]:
+        from . import _abi
+        self.check()
+        shares = self._all_shares()
+        if shares is not None:
+            ns = sh.TX_NAMESPACE if flag == _abi.SEQ_TX else sh.PAY_FOR_BLOB_NAMESPACE
+            return sh.parse_txs([s for s in shares if s.namespace() == ns])
+        out = []
+        for j in self.sequences(flag):
+            out.extend(compact_units(self._payload(j), int(self.records["reserved"][j])))
+        return out
+
+    def txs(self) -> List[bytes]:
+        """shares.parse_txs of the tx namespace's shares."""
+        from . import _abi
+        return self._units(_abi.SEQ_TX)
+
+    def wrapped_pfbs(self) -> List[bytes]:
+        """Square.wrapped_pfbs: shares.parse_txs of the PFB namespace's shares."""
+        from . import _abi
+        return self._units(_abi.SEQ_PFB)
+
+    def _run(self, flag: int):
+        """The records of one compact namespace as get_share_range_for_namespace
+        sees its shares: (first record, number of records, share range), or None
+        when no share has the namespace."""
+        ns = sh.TX_NAMESPACE if flag == 2 else sh.PAY_FOR_BLOB_NAMESPACE
+        idx = (self.records["flags"] & flag != 0).nonzero()[0]
+        if len(idx) == 0:
+            return None
+        a, b = int(idx[0]), int(idx[-1])
+        if b - a + 1 != len(idx):
+            return a, len(idx), None  # not one run of shares: the host route
+        r = self.records
+        return a, len(idx), Range(int(r["first"][a]), int(r["first"][b] + r["count"][b]))
+
+    def deconstruct(self, pfb_blob_sizes: Callable[[bytes], Sequence[int]]) -> List[bytes]:
+        """square.deconstruct on the records: the same checks in the same order
+        with the same messages.  A square that the records do not settle (a tx
+        or PFB namespace of several sequences, a share of another version,
+        shares out of namespace order, a share index that is not the first
+        share of a blob of the declared size) takes the host route: its shares
+        are fetched and square.deconstruct runs on them."""
+        from . import _abi
+        self.check()
+        r, total = self.records, self.k * self.k
+
+        def host_route():
+            return deconstruct(self._fetch(0, total), pfb_blob_sizes)
+
+        ns = [bytes(x[:sh.NAMESPACE_SIZE]) for x in r["ns"]]
+        if int(self.summary[2]) >= 0 or self.k == 1 or any(a > b for a, b in zip(ns, ns[1:])):
+            return host_route()
+        tx, pfb = self._run(_abi.SEQ_TX), self._run(_abi.SEQ_PFB)
+        for run in (tx, pfb):
+            if run is not None and (run[1] != 1 or r["flags"][run[0]] & _abi.SEQ_PADDING):
+                return host_route()
+        tr = Range() if tx is None else tx[2]
+        if tr.start != 0:
+            raise ShareError(f"expected txs to start at index 0, but got {tr.start}")
+        txs = [] if tx is None else compact_units(self._payload(tx[0]), int(r["reserved"][tx[0]]))
+        if pfb is None:
+            return txs
+        if pfb[2].start != tr.end:
+            raise ShareError(f"expected PFBs to start directly after non PFBs at index {tr.end}, but got "
+                             f"{pfb[2].start - tr.end}")
+        firsts = r["first"]
+        for i, wb in enumerate(compact_units(self._payload(pfb[0]), int(r["reserved"][pfb[0]]))):
+            iw, ok = btx.unmarshal_index_wrapper(wb)
+            if not ok:
+                raise ShareError(f"expected wrapped PFB at index {i}")
+            if not iw.share_indexes:
+                raise ShareError(f"wrapped PFB {i} has no blobs attached")
+            sizes = list(pfb_blob_sizes(iw.tx))
+            if len(sizes) != len(iw.share_indexes):
+                raise ShareError(f"expected PFB to have {len(iw.share_indexes)} blob sizes, but got {len(sizes)}")
+            blobs = []
+            for j, si in enumerate(iw.share_indexes):
+                at = int(firsts.searchsorted(si))
+                if at >= len(r) or int(firsts[at]) != si or not r["flags"][at] & _abi.SEQ_SPARSE \
+                        or r["flags"][at] & _abi.SEQ_PADDING \
+                        or int(r["count"][at]) != sh.sparse_shares_needed(sizes[j]):
+                    return host_route()
+                blobs.append(Blob.new(ns[at], self._payload(at), 0))
+            txs.append(btx.marshal_blob_tx(iw.tx, *blobs))
+        return txs
+
+
+def scan_native(ods, k: Optional[int] = None, seq_cap: Optional[int] = None, row_pitch: Optional[int] = None):
+    """dagpu_square_scan_host of one square (a uint8 array, or a list of
+    512-byte shares): (k, records[:min(n_sequences, seq_cap)], summary (8,)
+    int32).  Raises nothing for a square the reference refuses: the summary
+    tells."""
+    import numpy as np
+
+    from . import _abi
+    L = _abi.lib()
+    if not hasattr(ods, "dtype"):
+        ods = np.frombuffer(b"".join(s.to_bytes() if isinstance(s, Share) else bytes(s) for s in ods), np.uint8)
+    ods = np.ascontiguousarray(ods, np.uint8).reshape(-1)
+    pitch = row_pitch
+    if k is None:
+        k = math.isqrt(ods.size // sh.SHARE_SIZE)
+    if pitch is None:
+        pitch = k * sh.SHARE_SIZE
+    if ods.size < (k - 1) * pitch + k * sh.SHARE_SIZE:
+        raise ValueError("ods holds less than one square of this width")
+    cap = k * k if seq_cap is None else seq_cap
+    rec = np.zeros(max(cap, 1), seq_dtype())
+    summary = np.zeros(_abi.SCAN_SUMMARY_WORDS, np.int32)
+    rc = L.dagpu_square_scan_host(k, 1, _abi.addr(ods), k * pitch, pitch, cap, _abi.addr(rec), _abi.addr(summary))
+    if rc != 0:
+        raise ValueError(f"dagpu_square_scan_host: status {rc}: {L.dagpu_last_error(None).decode()}")
+    return k, rec[:min(int(summary[3]), cap)], summary
+
+
+def parse_native(ods, k: Optional[int] = None) -> ParsedSquare:
+    """One square on the host (a uint8 array of k*k*512 bytes, or a list of
+    shares) scanned by the host executor: a ParsedSquare whose blobs(), txs(),
+    wrapped_pfbs() and deconstruct() equal the mirror's parse_blobs, parse_txs
+    and deconstruct of the same shares."""
+    import numpy as np
+    if not hasattr(ods, "dtype"):
+        ods = np.frombuffer(b"".join(s.to_bytes() if isinstance(s, Share) else bytes(s) for s in ods), np.uint8)
+    k, rec, summary = scan_native(ods, k)
+    rows = np.ascontiguousarray(ods, np.uint8).reshape(k * k, sh.SHARE_SIZE)
+
+    def payload(j):
+        r = rec[j]
+        first, count, n = int(r["first"]), int(r["count"]), int(r["payload"])
+        head = 38 if r["flags"] & 6 else 34  # compact / sparse start share
+        parts = [rows[first, head:]] + [rows[s, head - 4:] for s in range(first + 1, first + count)]
+        return np.concatenate(parts)[:n].tobytes()
+
+    def fetch(a, b):
+        return [Share(rows[i].tobytes()) for i in range(a, min(b, k * k))]
+
+    return ParsedSquare(k, rec, summary, payload, fetch)
+
+
+def deconstruct_device(squares, pfb_blob_sizes: Callable[[bytes], Sequence[int]]) -> List[List[bytes]]:
+    """square.Deconstruct of every square of a device.DeviceSquares, from where
+    it lies in HBM: scan, gather of every blob and both tx streams, download of
+    that payload alone, then the checks of deconstruct on the records."""
+    return squares.deconstruct(pfb_blob_sizes)

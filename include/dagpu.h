@@ -792,6 +792,135 @@ int dagpu_blob_commitments_device(dagpu_ctx* ctx, uint32_t k, size_t n, size_t n
                                   void* d_workspace, void* stream);
 int dagpu_square_plan_blobs(const uint8_t* plan, size_t plan_bytes, uint32_t* out, size_t cap, size_t* nblob);
 
+/* ---- Square read: txs and blobs back out of squares resident in HBM -------
+ * The opposite direction of dagpu_square_write_device: square.Deconstruct
+ * (pkg/square/square.go:65-155) split into a scan of the shares
+ * (shares.ParseShares, pkg/shares/parse.go:42-97), a gather of the payload that
+ * was asked for, and the serial walk over the tx streams (parseRawData,
+ * pkg/shares/parse_compact_shares.go:47-66), which stays on the host.  The
+ * arithmetic is csrc/square_read.hpp, shared by the host executor and the
+ * kernels (csrc/square_read.hip).
+ *
+ * Squares are addressed as in dagpu_square_write_device (square i at
+ * d_squares + i * square_stride, rows row_pitch apart: the packed ODS batch or
+ * Q0 inside an EDS batch), with its limits, alignment checks and messages.
+ *
+ * dagpu_square_scan_device / dagpu_square_scan_host:
+ * shares.ParseShares(shares, ignorePadding = false) of n squares of width k.
+ * Of each share the first 38 bytes count (pkg/shares/shares.go:60-200): the
+ * namespace (29 B), the info byte (share version << 1 | sequence start), on a
+ * start share the big-endian sequence length, on a compact share (tx or PFB
+ * namespace) the big-endian reserved bytes; Share.IsPadding (shares.go:115-143)
+ * is "start share of sequence length 0, or the tail padding or the primary
+ * reserved padding namespace"; the content is the last 474 (compact start),
+ * 478 (compact continuation, sparse start) or 482 bytes of the share.  A
+ * sequence is a start share and the continuation shares up to the next start
+ * share; sequences never cross squares.
+ * Records: sequence j of square i, in share order, at d_records[i * seq_cap +
+ * j], j < min(n_sequences, seq_cap); other records are not written.  flags:
+ * exactly one of DAGPU_SEQ_SPARSE / _TX / _PFB; DAGPU_SEQ_PADDING for a
+ * sequence of one share that IsPadding (ShareSequence.isPadding,
+ * share_sequence.go:44-52); the first share's version from bit
+ * DAGPU_SEQ_VERSION_SHIFT.  reserved_bytes: the first share's, compact only.
+ * payload_len: 0 for padding, sequence_len for a blob, 474 + 478 (count - 1)
+ * for a compact sequence (the content of all its shares, uncut: extractRawData,
+ * parse_compact_shares.go:72-86, does not cut at the sequence length either).
+ * Summary, 8 int32 per square: {code, index, the lowest share whose share
+ * version is not 0 or -1, n_sequences, n_blob_sequences, blob_payload_bytes,
+ * compact_payload_bytes, 0}; the two byte totals are the sums over the
+ * non-padding sparse / compact sequences of payload_len rounded up to 16,
+ * which is what dagpu_square_read_device needs for them, and mean something
+ * only when code is DAGPU_SCAN_OK.  ParseShares ignores share versions;
+ * ParseBlobs and ParseTxs refuse one that is not 0 (parse_compact_shares.go:35-42,
+ * parse_sparse_shares.go:37-41), so the third word tells whether they would.
+ * code / index: the first error in the reference's order.
+ *   pass 1, ascending share i (parse.go:51-75):
+ *     DAGPU_SCAN_NAMESPACE     namespace.From rejects share i's namespace: not
+ *                              version 0 with 18 zero ID bytes, nor version 255
+ *                              (pkg/namespace/namespace.go:40-58, :95-113)
+ *     DAGPU_SCAN_INCONSISTENT  share i is a continuation and no start share
+ *                              precedes it, or its namespace differs from that
+ *                              of the nearest start share before it
+ *     the lowest i wins; on one share NAMESPACE comes first
+ *   pass 2, if pass 1 found nothing (parse.go:77-82, share_sequence.go:54-76):
+ *     DAGPU_SCAN_LENGTH        index = the first share of the lowest sequence
+ *                              that is not padding and whose share count is not
+ *                              CompactSharesNeeded / SparseSharesNeeded of its
+ *                              sequence length (share_sequence.go:106-142)
+ *   then DAGPU_SCAN_OVERFLOW   n_sequences > seq_cap; index = n_sequences
+ *                              (seq_cap = k*k never overflows)
+ * summary_out (HOST, may be NULL) receives a copy of the summary and makes the
+ * call wait for it; without it, and with a workspace, everything is only
+ * enqueued on `stream` (four launches).  d_records and d_summary are 16-B
+ * aligned.  d_workspace: dagpu_square_scan_workspace_size(k, n) bytes, 16-B
+ * aligned; NULL: the library allocates it and waits.  A refusal returns
+ * DAGPU_ERR_ARG with a message and enqueues nothing.  The host executor
+ * computes the same records and summary serially; it needs no context and no
+ * device (message: dagpu_last_error(NULL)).
+ *
+ * dagpu_square_read_device: the payload of the sequences that were asked for.
+ * Selected: the non-padding sequences, of squares whose code is DAGPU_SCAN_OK,
+ * whose class is in class_mask (DAGPU_READ_BLOBS: sparse; DAGPU_READ_COMPACT:
+ * tx and PFB) and whose namespace is one of the n_ns HOST namespaces (29 B
+ * each; NULL / 0: every namespace).  In (square, share) order, selected
+ * sequence m has d_selected[m] = its index into the record table, and
+ * d_offsets[m] = its 16-B aligned offset into d_payload, the sum of the
+ * earlier ones' payload_len rounded up to 16.  d_totals = {n_selected,
+ * payload_bytes (that sum over all of them), overflow}.  A sequence whose
+ * payload would end past payload_cap is not gathered and sets overflow = 1; the
+ * others are.  A blob yields its sequence_len bytes (478 of its first share,
+ * 482 of each continuation, the last one cut), a compact sequence the content
+ * of all its shares.  Bytes between payloads and past them are not written.
+ * d_selected and d_offsets hold n * seq_cap entries, d_totals 3.  d_workspace:
+ * dagpu_square_read_workspace_size(k, n, seq_cap, n_ns) bytes, 16-B aligned; with
+ * it the call is enqueued on `stream` (four launches) and returns once the
+ * namespace list has left host memory; with NULL the library allocates it and
+ * waits.
+ *
+ * dagpu_compact_units: parseRawData over a compact sequence's payload: the
+ * units (txs, or wrapped PFBs) from the first share's reserved bytes on.
+ * first_unit is that reserved value, a byte index into the first share: 0
+ * gives no units (Share.RawDataUsingReserved), 38 .. 511 starts at payload
+ * byte first_unit - 38, anything else is DAGPU_ERR_ARG.  Each unit is a
+ * uvarint length read as ParseDelimiter does (pkg/shares/utils.go:92-117: a
+ * 10-byte zero-padded window, skipping the value's canonical length) and that
+ * many bytes; the walk stops at a length of 0 or one longer than what is left.
+ * out_off[i] / out_len[i]: unit i's bytes in `stream`.  *n is set even when cap
+ * is too small, which returns DAGPU_ERR_ARG; a varint that overflows 64 bits
+ * is DAGPU_ERR_SQUARE with the reference's message.  No context, no device. */
+#define DAGPU_SCAN_OK 0
+#define DAGPU_SCAN_NAMESPACE 1
+#define DAGPU_SCAN_INCONSISTENT 2
+#define DAGPU_SCAN_LENGTH 3
+#define DAGPU_SCAN_OVERFLOW 4
+#define DAGPU_SCAN_SUMMARY_WORDS 8
+#define DAGPU_SEQ_SPARSE 1
+#define DAGPU_SEQ_TX 2
+#define DAGPU_SEQ_PFB 4
+#define DAGPU_SEQ_PADDING 8
+#define DAGPU_SEQ_VERSION_SHIFT 8
+#define DAGPU_READ_BLOBS 1
+#define DAGPU_READ_COMPACT 2
+typedef struct dagpu_seq_record {
+  uint8_t ns[32]; /* 29 bytes, zero padded */
+  uint32_t first_share, share_count, sequence_len, flags, reserved_bytes, payload_len;
+  uint32_t pad[2];
+} dagpu_seq_record; /* 64 bytes */
+size_t dagpu_square_scan_workspace_size(uint32_t k, size_t n);
+int dagpu_square_scan_device(dagpu_ctx* ctx, uint32_t k, size_t n, const uint8_t* d_squares, size_t square_stride,
+                             size_t row_pitch, uint32_t seq_cap, dagpu_seq_record* d_records, int32_t* d_summary,
+                             int32_t* summary_out /* HOST, may be NULL */, void* d_workspace, void* stream);
+int dagpu_square_scan_host(uint32_t k, size_t n, const uint8_t* squares, size_t square_stride, size_t row_pitch,
+                           uint32_t seq_cap, dagpu_seq_record* records, int32_t* summary);
+size_t dagpu_square_read_workspace_size(uint32_t k, size_t n, uint32_t seq_cap, size_t n_ns);
+int dagpu_square_read_device(dagpu_ctx* ctx, uint32_t k, size_t n, const uint8_t* d_squares, size_t square_stride,
+                             size_t row_pitch, uint32_t seq_cap, const dagpu_seq_record* d_records,
+                             const int32_t* d_summary, const uint8_t* namespaces /* HOST, may be NULL */, size_t n_ns,
+                             uint32_t class_mask, uint32_t* d_selected, uint64_t* d_offsets, uint64_t* d_totals,
+                             uint8_t* d_payload, size_t payload_cap, void* d_workspace, void* stream);
+int dagpu_compact_units(const uint8_t* stream, size_t len, uint32_t first_unit, uint64_t* out_off, uint64_t* out_len,
+                        size_t cap, size_t* n);
+
 #ifdef __cplusplus
 }
 #endif
