@@ -106,6 +106,12 @@ EXPORTS = (
     "dagpu_col_nodes_device",
     "dagpu_nmt_prove_workspace_size",
     "dagpu_nmt_prove_batch_device",
+    "dagpu_proof_store_size",
+    "dagpu_proof_store_workspace_size",
+    "dagpu_proof_store_device",
+    "dagpu_nmt_prove_squares_workspace_size",
+    "dagpu_nmt_prove_squares_device",
+    "dagpu_share_proof_requests",
     "dagpu_nmt_verify_namespace",
     "dagpu_nmt_verify_namespace_batch",
     "dagpu_nmt_verify_namespace_workspace_size",
@@ -127,6 +133,8 @@ SEQ_RECORD_BYTES = 64
 READ_BLOBS, READ_COMPACT = 1, 2
 
 PROVE_REQ_WORDS = 4
+PROVE_SQ_REQ_WORDS = 5
+MERKLE_DESC_WORDS = 6
 NMT_DESC_WORDS = 8
 NMT_NS_DESC_WORDS = 9
 NS_OUTSIDE, NS_PRESENT, NS_ABSENT = 0, 1, 2
@@ -289,6 +297,16 @@ def lib() -> ctypes.CDLL:
         L.dagpu_nmt_prove_workspace_size.restype = sz
         L.dagpu_nmt_prove_batch_device.argtypes = [vp, ctypes.c_uint32, sz, vp, vp, vp, vp, vp, sz, vp, vp, sz, vp,
                                                    ctypes.POINTER(sz), vp, vp]
+        L.dagpu_proof_store_size.argtypes = [ctypes.c_uint32, sz, ctypes.POINTER(sz), ctypes.POINTER(sz)]
+        L.dagpu_proof_store_size.restype = sz
+        L.dagpu_proof_store_workspace_size.argtypes = [ctypes.c_uint32, sz]
+        L.dagpu_proof_store_workspace_size.restype = sz
+        L.dagpu_proof_store_device.argtypes = [vp, ctypes.c_uint32, sz, vp, sz, vp, vp, vp]
+        L.dagpu_nmt_prove_squares_workspace_size.argtypes = [sz]
+        L.dagpu_nmt_prove_squares_workspace_size.restype = sz
+        L.dagpu_nmt_prove_squares_device.argtypes = [vp, ctypes.c_uint32, sz, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz,
+                                                     vp, vp, vp, vp, vp, ctypes.POINTER(sz), vp, vp]
+        L.dagpu_share_proof_requests.argtypes = [ctypes.c_uint32, sz, sz, vp, vp, sz, vp, ctypes.POINTER(sz)]
         L.dagpu_nmt_verify_namespace.argtypes = [vp, vp, sz, sz, i64, i64, vp, sz, vp, vp]
         L.dagpu_nmt_verify_namespace_batch.argtypes = [vp, sz, vp, vp, sz, vp, sz, sz, vp, sz, vp, sz, vp, sz, vp]
         L.dagpu_nmt_verify_namespace_workspace_size.argtypes = [sz, sz]

@@ -6,7 +6,7 @@ already resident in HBM and only the roots/DAH (or nothing) come back.
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -114,6 +114,173 @@ def nmt_prove_batch_device(nodes, requests, eds: Optional[torch.Tensor] = None, 
     if rc != 0:
         raise DAError(rc, c.last_error())
     return out_nodes[:total.value * ROOT], out_ns, out_shares, desc
+
+
+class StoreSquare:
+    """One square of a ProofStore with the attributes of an
+    inclusion.EDSAxisNodes (ctx, k, w, eds, nodes, col_inner, col_roots()), all
+    views into the store and the batch: what nmt_prove_batch_device,
+    proof.prove_ranges, proof.prove_namespaces and nmt_namespace_ranges_device
+    take in its place.  Nothing is hashed."""
+
+    def __init__(self, store: "ProofStore", i: int):
+        self.ctx, self.k, self.w = store.ctx, store.k, store.w
+        self.eds = store.eds[i * store.square_stride:i * store.square_stride + store.w * store.w * 512]
+        self.nodes = store.store[i * store.row_bytes:(i + 1) * store.row_bytes]
+        self.col_inner = store.store[store.col_off + i * store.col_bytes:store.col_off + (i + 1) * store.col_bytes]
+
+    def col_roots(self) -> torch.Tensor:
+        """(2k, 96) view of the column roots: the top level of the column store."""
+        return self.col_inner.view(-1, 96)[-self.w:]
+
+
+class ProofStore:
+    """dagpu_proof_store_device: every row-tree and column-tree node and the
+    DAH tree of ALL squares of a batch in one device buffer, built by a number
+    of launches that does not depend on the batch (enqueued on `stream`, no
+    sync).  eds_batch: a contiguous cuda uint8 tensor holding the extended
+    squares, square i at byte i * square_stride (default: back to back).
+
+    store:  the buffer; square i's row / column slices are byte for byte the
+            stores of inclusion.EDSAxisNodes (see square(i))
+    n, k, w, row_bytes, col_bytes, dah_bytes, col_off, dah_off: its layout"""
+
+    def __init__(self, k: int, eds_batch: torch.Tensor, square_stride: Optional[int] = None,
+                 ctx: Optional[Context] = None, stream: Optional[torch.cuda.Stream] = None):
+        import ctypes
+        self.ctx = ctx or default_context()
+        self.k, self.w = int(k), 2 * int(k)
+        one = self.w * self.w * 512
+        if not isinstance(eds_batch, torch.Tensor) or not eds_batch.is_cuda or eds_batch.dtype != torch.uint8 \
+                or not eds_batch.is_contiguous():
+            raise ValueError("eds_batch must be a contiguous cuda uint8 tensor")
+        self.eds = eds_batch.view(-1)
+        self.square_stride = one if square_stride is None else int(square_stride)
+        if self.square_stride < one or self.square_stride % 16:
+            raise ValueError("square_stride must be a multiple of 16 B and at least one extended square")
+        self.n = 0 if self.eds.numel() < one else 1 + (self.eds.numel() - one) // self.square_stride
+        L = self.ctx._L
+        col_off, dah_off = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        size = L.dagpu_proof_store_size(self.k, self.n, ctypes.byref(col_off), ctypes.byref(dah_off))
+        if size == 0:
+            raise DAError(_abi.ERR_ARG, f"no proof store for k = {k} and {self.n} squares")
+        self.col_off, self.dah_off = col_off.value, dah_off.value
+        self.row_bytes, self.col_bytes = L.dagpu_row_nodes_size(self.k), L.dagpu_col_nodes_size(self.k)
+        self.dah_bytes = (4 * self.w - 1) * 32
+        dev = self.eds.device
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        with torch.cuda.stream(s):
+            self.store = torch.empty((size,), dtype=torch.uint8, device=dev)
+            ws = torch.empty((L.dagpu_proof_store_workspace_size(self.k, self.n),), dtype=torch.uint8, device=dev)
+        self.ctx.check(L.dagpu_proof_store_device(self.ctx.handle, self.k, self.n, _abi.addr(self.eds),
+                                                  self.square_stride, _abi.addr(self.store), _abi.addr(ws),
+                                                  _stream_handle(s)))
+
+    def square(self, i: int) -> StoreSquare:
+        if not 0 <= i < self.n:
+            raise IndexError(f"square {i} of {self.n}")
+        return StoreSquare(self, i)
+
+    def dah_tree(self) -> torch.Tensor:
+        """(n, 8k - 1, 32) view of the DAH region: per square the 4k leaf
+        hashes, then each level above; the last digest is the data root."""
+        return self.store[self.dah_off:self.dah_off + self.n * self.dah_bytes].view(self.n, 4 * self.w - 1, 32)
+
+    def data_roots(self) -> torch.Tensor:
+        """(n, 32) view of the data roots: the top of each square's DAH tree."""
+        return self.dah_tree()[:, -1, :]
+
+
+class SquaresProofs(NamedTuple):
+    """What nmt_prove_squares_device returns: uint8 device tensors (shares None
+    without shares=True; axis_roots, leaf_hashes and aunts None without
+    to_data_root=True) and the two HOST descriptor arrays."""
+    nodes: torch.Tensor                  # 90 B per proof node
+    namespaces: torch.Tensor             # 29 B per request
+    shares: Optional[torch.Tensor]       # 512 B per proven cell
+    axis_roots: Optional[torch.Tensor]   # 90 B per request
+    leaf_hashes: Optional[torch.Tensor]  # 32 B per request
+    aunts: Optional[torch.Tensor]        # log2(4k) x 32 B per request
+    desc: "object"                       # (n, 8) int64: nmt_verify_batch_device, roots table = axis_roots
+    mdesc: "object"                      # (n, 6) int64: dagpu_merkle_verify_batch, roots = store.data_roots()
+
+
+def nmt_prove_squares_device(store: ProofStore, requests, shares: bool = True, to_data_root: bool = True,
+                             ctx: Optional[Context] = None, stream: Optional[torch.cuda.Stream] = None,
+                             workspace: Optional[torch.Tensor] = None) -> SquaresProofs:
+    """dagpu_nmt_prove_squares_device: nmt ProveRange for many (square, axis,
+    index, start, end) requests across the squares of a ProofStore, and with
+    to_data_root the merkle proof of each proven tree's root under its
+    square's data root, enqueued on `stream` (no sync of the results).
+    requests: (n, 5) int64-like on the HOST.  Outputs as nmt_prove_batch_device,
+    request by request; see SquaresProofs."""
+    import ctypes
+
+    import numpy as np
+    c = ctx or store.ctx
+    req = np.ascontiguousarray(np.asarray(requests, dtype=np.int64).reshape(-1, _abi.PROVE_SQ_REQ_WORDS))
+    n = int(req.shape[0])
+    w, dev = store.w, store.store.device
+    m = w.bit_length() - 1
+    start, last = req[:, 3].clip(0, w), (req[:, 4] - 1).clip(0, w - 1)
+
+    def popcount(v):
+        return np.unpackbits(v.astype(">u4").view(np.uint8)).reshape(len(v), 32).sum(axis=1)
+
+    # capacities from the requests as given; the library validates them
+    nodes_cap = int((popcount(start) + m - popcount(last)).sum()) if n else 0
+    shares_cap = int((req[:, 4] - req[:, 3]).clip(0, w).sum()) if shares else 0
+    la = m + 1  # log2(4k) aunts per proof
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    need = c._L.dagpu_nmt_prove_squares_workspace_size(n)
+    with torch.cuda.stream(s):
+        out_nodes = torch.empty((nodes_cap * ROOT,), dtype=torch.uint8, device=dev)
+        out_ns = torch.empty((n * 29,), dtype=torch.uint8, device=dev)
+        out_shares = torch.empty((shares_cap * 512,), dtype=torch.uint8, device=dev) if shares else None
+        out_roots = torch.empty((n * ROOT,), dtype=torch.uint8, device=dev) if to_data_root else None
+        out_lh = torch.empty((n * 32,), dtype=torch.uint8, device=dev) if to_data_root else None
+        out_aunts = torch.empty((n * la * 32,), dtype=torch.uint8, device=dev) if to_data_root else None
+        if workspace is None:
+            workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+    if workspace.numel() < need:
+        raise ValueError("workspace smaller than dagpu_nmt_prove_squares_workspace_size")
+    desc = np.zeros((n, _abi.NMT_DESC_WORDS), np.int64)
+    mdesc = np.zeros((n, _abi.MERKLE_DESC_WORDS), np.int64) if to_data_root else None
+    total = ctypes.c_size_t(0)
+    rc = c._L.dagpu_nmt_prove_squares_device(
+        c.handle, store.k, store.n, n, _abi.addr(req), _abi.addr(store.eds) if shares else None,
+        store.square_stride, _abi.addr(store.store), _abi.addr(out_nodes), nodes_cap, _abi.addr(out_ns),
+        _abi.addr(out_shares) if shares else None, shares_cap, _abi.addr(out_roots) if to_data_root else None,
+        _abi.addr(out_lh) if to_data_root else None, _abi.addr(out_aunts) if to_data_root else None,
+        _abi.addr(desc), _abi.addr(mdesc) if to_data_root else None, ctypes.byref(total), _abi.addr(workspace),
+        _stream_handle(s))
+    if rc != 0:
+        raise DAError(rc, c.last_error())
+    return SquaresProofs(out_nodes[:total.value * ROOT], out_ns, out_shares, out_roots, out_lh, out_aunts, desc,
+                         mdesc)
+
+
+def share_proof_requests(k: int, n_sq: int, ranges):
+    """dagpu_share_proof_requests: NewShareInclusionProof's row split of
+    (square, start, end) ranges of row-major ODS share indexes.  Returns (req
+    (n_req, 5) int64, span (n + 1,) int64): range i owns requests
+    span[i] .. span[i + 1].  Host arithmetic; raises DAError(ERR_ARG) on an
+    invalid range."""
+    import ctypes
+
+    import numpy as np
+    sreq = np.ascontiguousarray(np.asarray(ranges, dtype=np.int64).reshape(-1, 3))
+    n = int(sreq.shape[0])
+    # a range touches at most (end - 1) // k - start // k + 1 rows
+    cap = int(((sreq[:, 2] - 1).clip(0, k * k) // k - sreq[:, 1].clip(0, k * k) // k + 1).clip(0).sum()) if n else 0
+    req = np.zeros((max(cap, 1), _abi.PROVE_SQ_REQ_WORDS), np.int64)
+    span = np.zeros(n + 1, np.int64)
+    n_req = ctypes.c_size_t(0)
+    rc = _abi.lib().dagpu_share_proof_requests(k, n_sq, n, _abi.addr(sreq), _abi.addr(req), cap, _abi.addr(span),
+                                               ctypes.byref(n_req))
+    if rc != 0:
+        raise DAError(rc, f"invalid share range for {n_sq} squares of width {k}")
+    return req[:n_req.value], span
 
 
 def _ns_table(namespaces):
@@ -457,6 +624,8 @@ class DeviceSquares:
         self._src_lens = None
         # scan(): (records, summary, host summary, (buffer, square_stride, row_pitch))
         self._scan = None
+        # proof_store(): the ProofStore of self.eds, until the squares change
+        self._proof_store = None
 
     def q0(self) -> torch.Tensor:
         """(n, k, k*512) view of Q0 inside the EDS buffer."""
@@ -466,6 +635,7 @@ class DeviceSquares:
     def load_ods(self, ods) -> None:
         """Copy n ODS (anything viewable as (n, k*k*512) uint8) to where extend()
         reads them: self.ods, or Q0 of the EDS when in_place."""
+        self._proof_store = None
         src = ods if isinstance(ods, torch.Tensor) else torch.from_numpy(ods)
         src = src.reshape(self.n, self.k, self.k * 512)
         if self.in_place:
@@ -487,6 +657,7 @@ class DeviceSquares:
         from . import square as sq
         if len(blocks) != self.n:
             raise ValueError(f"{self.n} blocks expected, got {len(blocks)}")
+        self._proof_store = None
         if self.ods is None and not self.in_place:
             raise ValueError("no ODS buffer: DeviceSquares(with_ods=False) takes its input through extend_from")
         m = sq.SQUARE_SIZE_UPPER_BOUND if max_square_size is None else max_square_size
@@ -662,12 +833,79 @@ class DeviceSquares:
         return [p.deconstruct(pfb_blob_sizes)
                 for p in self._parsed(_abi.READ_BLOBS | _abi.READ_COMPACT, None, stream, from_eds)]
 
+    # ---- share proofs to the data root (dagpu_proof_store_device / dagpu_nmt_prove_squares_device) ----
+
+    def proof_store(self, stream: Optional[torch.cuda.Stream] = None) -> ProofStore:
+        """The ProofStore of self.eds: built once (enqueued on `stream`) and
+        kept until extend*, repair*, load_ods or load_txs change the squares."""
+        if self._proof_store is None:
+            self._proof_store = ProofStore(self.k, self.eds, ctx=self.ctx, stream=stream)
+        return self._proof_store
+
+    def share_proofs(self, ranges, namespaces=None, stream: Optional[torch.cuda.Stream] = None):
+        """proof.NewShareInclusionProof (pkg/proof/proof.go:58-165) for a list
+        of ranges = (square, start, end) of row-major ODS share indexes, spread
+        over the batch: a List[proof.ShareProof], each equal field for field to
+        proof.new_share_inclusion_proof of that square.  namespaces: one 29-B
+        namespace per range; None takes the namespace of the range's first
+        share, and a range whose shares carry different namespaces raises the
+        DAError of proof.parse_namespace.  One produce call and one download for
+        the whole list; nothing is hashed beyond the cached proof_store()."""
+        import numpy as np
+
+        from . import proof as pf
+        ranges = [tuple(int(v) for v in r) for r in ranges]
+        if namespaces is not None and len(namespaces) != len(ranges):
+            raise ValueError("one namespace per range")
+        if not ranges:
+            return []
+        req, span = share_proof_requests(self.k, self.n, ranges)
+        store = self.proof_store(stream)
+        s = stream if stream is not None else torch.cuda.current_stream(self.eds.device)
+        out = nmt_prove_squares_device(store, req, shares=True, to_data_root=True, ctx=self.ctx, stream=s)
+        parts = (out.nodes, out.shares, out.axis_roots, out.leaf_hashes, out.aunts)
+        with torch.cuda.stream(s):
+            host = torch.cat(parts).cpu().numpy().tobytes()
+        at = np.cumsum([0] + [t.numel() for t in parts])
+        nodes, cells, roots, hashes, aunts = (host[at[j]:at[j + 1]] for j in range(len(parts)))
+        la = (4 * self.k).bit_length() - 1
+        proofs = []
+        for i, (_, start, end) in enumerate(ranges):
+            rows = range(int(span[i]), int(span[i + 1]))
+            d = out.desc[rows.start:rows.stop]
+            data = [cells[512 * j:512 * (j + 1)] for j in range(int(d[0, 3]), int(d[-1, 3] + d[-1, 2]))]
+            ns = pf.parse_namespace(data, 0, len(data)) if namespaces is None else bytes(namespaces[i])
+            proofs.append(pf.ShareProof(
+                data=data,
+                share_proofs=[pf.NMTProof(int(q[0]), int(q[1]),
+                                          [nodes[90 * j:90 * (j + 1)] for j in range(int(q[5]), int(q[5] + q[4]))])
+                              for q in d],
+                namespace_id=ns[1:],
+                row_proof=pf.RowProof(
+                    [roots[90 * r:90 * (r + 1)] for r in rows],
+                    [pf.MerkleProof(4 * self.k, int(req[r, 2]), hashes[32 * r:32 * (r + 1)],
+                                    [aunts[32 * (r * la + a):32 * (r * la + a + 1)] for a in range(la)])
+                     for r in rows],
+                    start // self.k, (end - 1) // self.k),
+                namespace_version=ns[0]))
+        return proofs
+
+    def blob_proofs(self, rows=None, stream: Optional[torch.cuda.Stream] = None):
+        """One proof.ShareProof per blob of blob_table() (or of its selected
+        `rows`), to the data root of the blob's block: share_proofs over
+        (square, first_share, first_share + share_count)."""
+        rec, _ = self.blob_table()
+        if rows is not None:
+            rec = rec[list(rows)]
+        return self.share_proofs([(int(sq), int(a), int(a + c)) for sq, a, c in rec], stream=stream)
+
     def _ck(self, rc: int) -> None:
         if rc != 0:
             raise DAError(rc, self.ctx.last_error())
 
     def extend(self, stream: Optional[torch.cuda.Stream] = None) -> None:
         """ODS -> EDS -> roots -> DAH, enqueued on `stream` (no sync)."""
+        self._proof_store = None
         L = self.ctx._L
         self._ck(L.dagpu_extend_batch_device(
             self.ctx.handle, self.k, self.n, _abi.addr(self.ods), _abi.addr(self.eds),
@@ -682,6 +920,7 @@ class DeviceSquares:
         if m > self.n or ods.dtype != torch.uint8 or ods.device != self.eds.device \
                 or not ods.is_contiguous() or ods.numel() != m * self.k * self.k * 512:
             raise ValueError("ods must be a contiguous (m <= n, k*k*512) uint8 tensor on this device")
+        self._proof_store = None
         L = self.ctx._L
         self._ck(L.dagpu_extend_batch_device(
             self.ctx.handle, self.k, m, _abi.addr(ods), _abi.addr(self.eds),
@@ -690,6 +929,7 @@ class DeviceSquares:
         return m
 
     def extend_rs(self, stream: Optional[torch.cuda.Stream] = None) -> None:
+        self._proof_store = None
         self._ck(self.ctx._L.dagpu_extend_rs_device(
             self.ctx.handle, self.k, self.n, _abi.addr(self.ods), _abi.addr(self.eds),
             _stream_handle(stream)))
@@ -700,6 +940,7 @@ class DeviceSquares:
         present: (n, (2k)^2) uint8, updated in place; status: (n,) int32;
         byz (optional): (n, 4) int32 on the device -> failing axis per square
         (dagpu_repair_batch_device_ex)."""
+        self._proof_store = None
         L = self.ctx._L
         if byz is None:
             self._ck(L.dagpu_repair_batch_device(
@@ -722,6 +963,7 @@ class DeviceSquares:
         status / workspace as repair() (status and present indexed from
         `first`; workspace sized for `count` squares)."""
         import ctypes
+        self._proof_store = None
         count = self.n - first if count is None else count
         w = 2 * self.k
         h = ctypes.c_uint64(0)
@@ -742,6 +984,7 @@ class DeviceSquares:
         (which includes the repair) before it reuses their blocks, whichever
         stream allocated them."""
         js = stream if stream is not None else torch.cuda.current_stream()
+        self._proof_store = None
         try:
             self._ck(self.ctx._L.dagpu_repair_join(self.ctx.handle, handle, int(js.cuda_stream)))
         finally:

@@ -98,6 +98,48 @@ hipError_t launch_prove_emit(const ProveArgs& a, hipStream_t s);
 hipError_t launch_prove_namespaces(const ProveArgs& a, hipStream_t s);
 hipError_t launch_prove_shares(const ProveArgs& a, hipStream_t s);
 
+// The same producer across the squares of a batch proof store, with the
+// merkle half to the data root (dagpu_nmt_prove_squares_device).  Laid out by
+// share_proof_layout.hpp; the kernels check nothing.
+struct ProveSqArgs {
+  long n;                   // proofs
+  int w, logw;              // leaves per tree (2k) and log2 of it
+  const int64_t* req;       // n x {prove_pack_req word, square}
+  const int64_t* node_off;  // n + 1 prefix sums
+  const int64_t* leaf_off;  // n + 1 prefix sums
+  long n_nodes, n_leaves;
+  const uint8_t* store;     // the batch proof store
+  long row_bytes, col_bytes, dah_bytes;  // per square
+  long col_off, dah_off;    // region starts
+  const uint8_t* eds;       // square i at eds + i * square_stride
+  long square_stride;
+  uint8_t* nodes_out;       // n_nodes packed 90-B nodes
+  uint8_t* ns_out;          // n x 29 B or null
+  uint8_t* shares_out;      // n_leaves x 512 B or null
+  uint8_t* axis_roots_out;  // n x 90 B or null
+  uint8_t* leaf_hash_out;   // n x 32 B or null
+  uint8_t* aunts_out;       // n x log2(4k) x 32 B or null
+};
+hipError_t launch_prove_sq_emit(const ProveSqArgs& a, hipStream_t s);
+hipError_t launch_prove_sq_namespaces(const ProveSqArgs& a, hipStream_t s);
+hipError_t launch_prove_sq_shares(const ProveSqArgs& a, hipStream_t s);
+hipError_t launch_prove_sq_merkle(const ProveSqArgs& a, hipStream_t s);
+
+// Batch proof store (proof_store.hip): every row-tree and column-tree node
+// and the DAH tree of n squares, each level of all squares in one launch.
+struct ProofStoreArgs {
+  long n;             // squares
+  int k, w, logw;     // w = 2k
+  const uint8_t* eds; // square i at eds + i * square_stride
+  long square_stride;
+  uint8_t* store;
+  long row_bytes, col_bytes, dah_bytes;  // per square
+  long col_off, dah_off;                 // region starts
+};
+hipError_t launch_store_leaves(const ProofStoreArgs& a, hipStream_t s);
+hipError_t launch_store_level(const ProofStoreArgs& a, int L, hipStream_t s);      // 1 <= L <= logw, rows and columns
+hipError_t launch_store_dah_level(const ProofStoreArgs& a, int L, hipStream_t s);  // 0 <= L <= logw + 1
+
 // Share commitments from squares resident in HBM (blob_commit.hip).  Every
 // table was checked and laid out on the host (commit_layout.hpp); the kernels
 // check nothing.

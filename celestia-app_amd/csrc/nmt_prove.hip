@@ -20,12 +20,15 @@
 //   shares      32 lanes per proven cell, 16 B each: row ranges are contiguous
 //               in the EDS, column ranges strided by one EDS row
 // The host (trees.cpp) has validated every request; the kernels check nothing.
+// The prove_sq_* kernels below serve requests across the squares of a batch
+// proof store and add the merkle half to the data root.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "forest.hpp"
 #include "nmt_node.hpp"
 #include "prove_layout.hpp"
+#include "share_proof_layout.hpp"
 
 namespace dagpu {
 
@@ -107,6 +110,122 @@ __global__ __launch_bounds__(256) void prove_shares_kernel(ProveArgs a) {
   const long j = (long)r.start + (cell - a.leaf_off[i]);  // leaf of the tree
   const long src = r.axis == 0 ? (long)r.index * a.w + j : j * a.w + r.index;
   ((uint4*)(a.shares_out + cell * kShareSize))[q] = ((const uint4*)(a.eds + src * kShareSize))[q];
+}
+
+// ---------------------------------------------------------------------------
+// The same three kernels across the squares of a batch proof store
+// (dagpu_nmt_prove_squares_device; layout in share_proof_layout.hpp): request
+// i carries its square, whose row and column slices of the store are the two
+// stores above, and whose cells lie square_stride bytes after the previous
+// square's.  A fourth kernel copies the merkle half of a proof to the data
+// root (pkg/proof/proof.go:84-91): the axis root, its leaf hash in the DAH tree
+// and the log2(4k) aunts of leaf axis * 2k + index, leaf to root.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ ProveArgs prove_sq_view(const ProveSqArgs& a, long sq) {
+  ProveArgs v{};
+  v.w = a.w;
+  v.logw = a.logw;
+  v.row_nodes = a.store + sq * a.row_bytes;
+  v.col_inner = a.store + a.col_off + sq * a.col_bytes;
+  v.eds = a.eds + sq * a.square_stride;
+  return v;
+}
+
+__global__ __launch_bounds__(256) void prove_sq_emit_kernel(ProveSqArgs a) {
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= a.n_nodes) return;
+  const long i = prove_find(a.node_off, a.n, t);
+  const ProveReq r = prove_unpack((uint64_t)a.req[2 * i]);
+  int depth;
+  uint32_t pos;
+  prove_node_at(a.logw, r.start, r.end, (int)(t - a.node_off[i]), &depth, &pos);
+  const uint8_t* rec = prove_record(prove_sq_view(a, a.req[2 * i + 1]), r.axis, r.index, a.logw - depth, pos);
+  uint32_t mn[8], mx[8], dg[8];
+  prove_load8(rec, mn);
+  prove_load8(rec + 32, mx);
+  prove_load8(rec + 64, dg);
+  write_root(a.nodes_out + t * kNodeSize, mn, mx, dg);
+}
+
+__global__ __launch_bounds__(256) void prove_sq_ns_kernel(ProveSqArgs a) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.n) return;
+  const ProveReq r = prove_unpack((uint64_t)a.req[2 * i]);
+  uint32_t mn[8];
+  prove_load8(prove_record(prove_sq_view(a, a.req[2 * i + 1]), r.axis, r.index, 0, r.start), mn);
+  uint8_t* o = a.ns_out + i * kNsSize;
+#pragma unroll
+  for (int b = 0; b < kNsSize; b++) o[b] = (uint8_t)(mn[b >> 2] >> (8 * (b & 3)));
+}
+
+__global__ __launch_bounds__(256) void prove_sq_shares_kernel(ProveSqArgs a) {
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  const long cell = t >> 5;  // 32 lanes of 16 B per 512-B cell
+  if (cell >= a.n_leaves) return;
+  const int q = (int)(t & 31);
+  const long i = prove_find(a.leaf_off, a.n, cell);
+  const ProveReq r = prove_unpack((uint64_t)a.req[2 * i]);
+  const long j = (long)r.start + (cell - a.leaf_off[i]);  // leaf of the tree
+  const long src = r.axis == 0 ? (long)r.index * a.w + j : j * a.w + r.index;
+  const uint8_t* eds = a.eds + a.req[2 * i + 1] * a.square_stride;
+  ((uint4*)(a.shares_out + cell * kShareSize))[q] = ((const uint4*)(eds + src * kShareSize))[q];
+}
+
+// 2 (log2(4k) + 1) + 1 lanes per proof: two 16-B lanes for the leaf hash and for
+// each aunt, one lane for the packed 90-B axis root
+__global__ __launch_bounds__(256) void prove_sq_merkle_kernel(ProveSqArgs a) {
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  const int la = a.logw + 1;  // aunts per proof
+  const int per = 2 * (la + 1) + 1;
+  const long i = t / per;
+  if (i >= a.n) return;
+  const int q = (int)(t - i * per);
+  const ProveReq r = prove_unpack((uint64_t)a.req[2 * i]);
+  const long sq = a.req[2 * i + 1];
+  if (q == per - 1) {
+    if (!a.axis_roots_out) return;
+    const uint8_t* rec = prove_record(prove_sq_view(a, sq), r.axis, r.index, a.logw, 0);
+    uint32_t mn[8], mx[8], dg[8];
+    prove_load8(rec, mn);
+    prove_load8(rec + 32, mx);
+    prove_load8(rec + 64, dg);
+    write_root(a.axis_roots_out + i * kNodeSize, mn, mx, dg);
+    return;
+  }
+  const int item = q >> 1, half = q & 1;  // item 0: the leaf hash; item L + 1: the aunt at level L
+  const long leaves = 2L * a.w, leaf = (long)r.axis * a.w + r.index;
+  const uint4* dah = (const uint4*)(a.store + a.dah_off + sq * a.dah_bytes);
+  if (item == 0) {
+    if (a.leaf_hash_out) ((uint4*)a.leaf_hash_out)[2 * i + half] = dah[2 * leaf + half];
+  } else if (a.aunts_out) {
+    ((uint4*)a.aunts_out)[2 * (i * la + item - 1) + half] = dah[2 * dah_aunt_at(leaves, leaf, item - 1) + half];
+  }
+}
+
+hipError_t launch_prove_sq_emit(const ProveSqArgs& a, hipStream_t s) {
+  if (a.n_nodes <= 0) return hipSuccess;
+  hipLaunchKernelGGL(prove_sq_emit_kernel, dim3((unsigned)((a.n_nodes + 255) / 256)), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_prove_sq_namespaces(const ProveSqArgs& a, hipStream_t s) {
+  if (a.n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(prove_sq_ns_kernel, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_prove_sq_shares(const ProveSqArgs& a, hipStream_t s) {
+  if (a.n_leaves <= 0) return hipSuccess;
+  const long threads = a.n_leaves * 32;
+  hipLaunchKernelGGL(prove_sq_shares_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_prove_sq_merkle(const ProveSqArgs& a, hipStream_t s) {
+  if (a.n <= 0) return hipSuccess;
+  const long threads = a.n * (2 * (a.logw + 2) + 1);
+  hipLaunchKernelGGL(prove_sq_merkle_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, a);
+  return hipGetLastError();
 }
 
 hipError_t launch_prove_emit(const ProveArgs& a, hipStream_t s) {

@@ -19,6 +19,12 @@
 //                          trees of a resident square (pkg/proof/proof.go:87-150),
 //                          nodes selected on the device (nmt_prove.hip); request
 //                          checks and layout in prove_layout.hpp
+//   dagpu_proof_store_device / dagpu_nmt_prove_squares_device / dagpu_share_proof_requests
+//                          the same proofs for all n squares of a batch and on to the
+//                          data root (RowProof, pkg/proof/proof.go:84-91): one store
+//                          built with a launch count independent of n
+//                          (proof_store.hip), requests across squares; layout and
+//                          NewShareInclusionProof's row split in share_proof_layout.hpp
 //   dagpu_nmt_verify_namespace / dagpu_nmt_verify_namespace_batch(_device)
 //                          nmt Proof.VerifyNamespace: presence with completeness,
 //                          absence and empty proofs (rules stated in dagpu.h,
@@ -49,6 +55,7 @@
 #include "proof_verify.hpp"
 #include "prove_layout.hpp"
 #include "runtime.hpp"
+#include "share_proof_layout.hpp"
 
 namespace {
 
@@ -552,6 +559,145 @@ int dagpu_nmt_prove_batch_device(dagpu_ctx* ctx, uint32_t k, size_t n, const int
   if (desc_out) prove_fill_desc(k, n, req, lay, desc_out);
   if (n_nodes_total) *n_nodes_total = (size_t)lay.n_nodes;
   return DAGPU_OK;
+}
+
+size_t dagpu_proof_store_size(uint32_t k, size_t n, size_t* col_off, size_t* dah_off) {
+  ProofStoreLayout l;
+  if (k == 0 || !is_pow2(k) || k > (uint32_t)kMaxK || n == 0 || !proof_store_layout(k, n, &l)) return 0;
+  if (col_off) *col_off = l.col_off;
+  if (dah_off) *dah_off = l.dah_off;
+  return l.total;
+}
+
+size_t dagpu_proof_store_workspace_size(uint32_t k, size_t n) {
+  if (dagpu_proof_store_size(k, n, nullptr, nullptr) == 0) return 0;
+  return 256;  // the shapes are uniform: nothing is uploaded, the workspace is reserved
+}
+
+int dagpu_proof_store_device(dagpu_ctx* ctx, uint32_t k, size_t n, const uint8_t* d_eds, size_t square_stride,
+                             uint8_t* d_store, void* d_workspace, void* stream) {
+  if (!ctx) return DAGPU_ERR_ARG;
+  int rc = check_k(ctx, k);
+  if (rc) return rc;
+  ProofStoreLayout l;
+  if (n == 0 || !proof_store_layout(k, n, &l))
+    return set_err(ctx, DAGPU_ERR_ARG, "dagpu_proof_store_device: no squares, or a store beyond the address space");
+  if (!d_eds || !d_store || !d_workspace)
+    return set_err(ctx, DAGPU_ERR_ARG, "dagpu_proof_store_device: null buffer");
+  const size_t w = 2 * (size_t)k;
+  if ((((uintptr_t)d_eds | (uintptr_t)d_store | square_stride) & 15) != 0 || square_stride < w * w * kShareSize)
+    return set_err(ctx, DAGPU_ERR_ARG,
+                   "dagpu_proof_store_device: buffers and square_stride must be multiples of 16 B, squares must "
+                   "not overlap");
+  ProofStoreArgs a{};
+  a.n = (long)n;
+  a.k = (int)k;
+  a.w = (int)w;
+  a.logw = prove_log2((uint32_t)w);
+  a.eds = d_eds;
+  a.square_stride = (long)square_stride;
+  a.store = d_store;
+  a.row_bytes = (long)l.row_bytes;
+  a.col_bytes = (long)l.col_bytes;
+  a.dah_bytes = (long)l.dah_bytes;
+  a.col_off = (long)l.col_off;
+  a.dah_off = (long)l.dah_off;
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(ctx, launch_store_leaves(a, s));
+  for (int L = 1; L <= a.logw; L++) HIP_TRY(ctx, launch_store_level(a, L, s));
+  for (int L = 0; L <= a.logw + 1; L++) HIP_TRY(ctx, launch_store_dah_level(a, L, s));
+  return DAGPU_OK;
+}
+
+size_t dagpu_nmt_prove_squares_workspace_size(size_t n_req) {
+  // requests (2 words each) | node_off (n + 1) | leaf_off (n + 1), 8 B each
+  return ws_align256((4 * n_req + 2) * sizeof(int64_t)) + 256;
+}
+
+int dagpu_nmt_prove_squares_device(dagpu_ctx* ctx, uint32_t k, size_t n_sq, size_t n_req, const int64_t* req,
+                                   const uint8_t* d_eds, size_t square_stride, const uint8_t* d_store,
+                                   uint8_t* d_nodes_out, size_t nodes_cap, uint8_t* d_ns_out, uint8_t* d_shares_out,
+                                   size_t shares_cap, uint8_t* d_axis_roots_out, uint8_t* d_leaf_hash_out,
+                                   uint8_t* d_aunts_out, int64_t* desc_out, int64_t* mdesc_out,
+                                   size_t* n_nodes_total, void* d_workspace, void* stream) {
+  if (!ctx) return DAGPU_ERR_ARG;
+  int rc = check_k(ctx, k);
+  if (rc) return rc;
+  if (n_req == 0) {
+    if (n_nodes_total) *n_nodes_total = 0;
+    return DAGPU_OK;
+  }
+  ProofStoreLayout l;
+  if (n_sq == 0 || !proof_store_layout(k, n_sq, &l))
+    return set_err(ctx, DAGPU_ERR_ARG, "dagpu_nmt_prove_squares_device: no squares");
+  if (!req || !d_store || !d_workspace || (nodes_cap && !d_nodes_out) || (d_shares_out && !d_eds))
+    return set_err(ctx, DAGPU_ERR_ARG, "dagpu_nmt_prove_squares_device: null buffer");
+  if ((((uintptr_t)d_workspace | (uintptr_t)d_store | (uintptr_t)d_eds | (uintptr_t)d_shares_out |
+        (uintptr_t)d_leaf_hash_out | (uintptr_t)d_aunts_out | (d_shares_out ? square_stride : 0)) & 15) != 0 ||
+      ((((uintptr_t)d_nodes_out) | (uintptr_t)d_axis_roots_out) & 1) != 0)
+    return set_err(ctx, DAGPU_ERR_ARG, "dagpu_nmt_prove_squares_device: misaligned buffer");
+  const size_t w = 2 * (size_t)k;
+  if (d_shares_out && square_stride < w * w * kShareSize)
+    return set_err(ctx, DAGPU_ERR_ARG, "dagpu_nmt_prove_squares_device: square_stride smaller than a square");
+  ProveLayout lay;
+  size_t bad = 0;
+  const int pc = prove_squares_layout(k, n_sq, n_req, req, nodes_cap, d_shares_out != nullptr, shares_cap, &lay, &bad);
+  if (pc != kProveOk) {
+    const char* why = pc == kProveBadSquare  ? "square outside the batch"
+                      : pc == kProveBadAxis  ? "axis is not 0 or 1"
+                      : pc == kProveBadIndex ? "index outside the square"
+                      : pc == kProveBadRange ? "range is not 0 <= start < end <= 2k"
+                      : pc == kProveNodesCap ? "more proof nodes than nodes_cap"
+                                             : "more proven cells than shares_cap";
+    return set_err(ctx, DAGPU_ERR_ARG,
+                   (bad < n_req ? "proof request " + std::to_string(bad) + ": " : std::string("proof batch: ")) + why);
+  }
+  // device image: requests, then the two offset arrays
+  const size_t n = n_req;
+  std::vector<int64_t> meta(4 * n + 2);
+  for (size_t i = 0; i < n; i++) prove_squares_pack_req(req + i * kProveSqReqWords, &meta[2 * i]);
+  memcpy(meta.data() + 2 * n, lay.node_off.data(), (n + 1) * sizeof(int64_t));
+  memcpy(meta.data() + 3 * n + 1, lay.leaf_off.data(), (n + 1) * sizeof(int64_t));
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(ctx, hipMemcpyAsync(d_workspace, meta.data(), meta.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
+  HIP_TRY(ctx, hipStreamSynchronize(s));  // `meta` and the caller's requests may go
+  ProveSqArgs a{};
+  a.n = (long)n;
+  a.w = (int)w;
+  a.logw = prove_log2((uint32_t)w);
+  a.req = (const int64_t*)d_workspace;
+  a.node_off = a.req + 2 * n;
+  a.leaf_off = a.node_off + (n + 1);
+  a.n_nodes = (long)lay.n_nodes;
+  a.n_leaves = (long)lay.n_leaves;
+  a.store = d_store;
+  a.row_bytes = (long)l.row_bytes;
+  a.col_bytes = (long)l.col_bytes;
+  a.dah_bytes = (long)l.dah_bytes;
+  a.col_off = (long)l.col_off;
+  a.dah_off = (long)l.dah_off;
+  a.eds = d_eds;
+  a.square_stride = (long)square_stride;
+  a.nodes_out = d_nodes_out;
+  a.ns_out = d_ns_out;
+  a.shares_out = d_shares_out;
+  a.axis_roots_out = d_axis_roots_out;
+  a.leaf_hash_out = d_leaf_hash_out;
+  a.aunts_out = d_aunts_out;
+  HIP_TRY(ctx, launch_prove_sq_emit(a, s));
+  if (d_ns_out) HIP_TRY(ctx, launch_prove_sq_namespaces(a, s));
+  if (d_shares_out) HIP_TRY(ctx, launch_prove_sq_shares(a, s));
+  if (d_axis_roots_out || d_leaf_hash_out || d_aunts_out) HIP_TRY(ctx, launch_prove_sq_merkle(a, s));
+  if (desc_out) prove_squares_fill_desc(n, req, lay, desc_out);
+  if (mdesc_out) prove_squares_fill_mdesc(k, n, req, mdesc_out);
+  if (n_nodes_total) *n_nodes_total = (size_t)lay.n_nodes;
+  return DAGPU_OK;
+}
+
+int dagpu_share_proof_requests(uint32_t k, size_t n_sq, size_t n, const int64_t* sreq, int64_t* req_out, size_t cap,
+                               int64_t* span_out, size_t* n_req) {
+  if (k == 0 || !is_pow2(k) || k > (uint32_t)kMaxK || (n && (!sreq || !req_out))) return DAGPU_ERR_ARG;
+  return share_proof_requests(k, n_sq, n, sreq, req_out, cap, span_out, n_req) ? DAGPU_OK : DAGPU_ERR_ARG;
 }
 
 int dagpu_merkle_levels(dagpu_ctx* ctx, size_t n, const uint8_t* items, size_t item_len, uint8_t* out32,

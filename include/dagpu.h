@@ -542,6 +542,93 @@ int dagpu_nmt_prove_batch_device(dagpu_ctx* ctx, uint32_t k, size_t n, const int
                                  int64_t* desc_out, size_t* n_nodes_total, void* d_workspace,
                                  void* stream);
 
+/* ---- Share proofs to the data root from a whole batch of squares ----------
+ * A ShareProof (pkg/proof/proof.go:58-165) is the nmt range proof of each
+ * touched row under its row root (lines 127-140) plus a RowProof: the merkle
+ * proof of each of those row roots under DataAvailabilityHeader.Hash, from
+ * merkle.ProofsFromByteSlices over rowRoots || colRoots (lines 84-91; consumer
+ * x/blobstream/client/verify.go).  The reference recomputes the EDS and every
+ * tree per query; here one store holds them for all n squares of a batch.
+ *
+ * dagpu_proof_store_device fills d_store (dagpu_proof_store_size(k, n, ..)
+ * bytes, 16-B aligned) from n extended squares in device memory, square i at
+ * d_eds + i * square_stride (a multiple of 16 B, at least (2k)^2 * 512).  Three
+ * regions, square-major, starts 256-B aligned:
+ *   row store  offset 0, dagpu_row_nodes_size(k) bytes per square: byte for
+ *              byte what dagpu_row_nodes_device writes for that EDS
+ *   col store  offset *col_off, dagpu_col_nodes_size(k) bytes per square: byte
+ *              for byte what dagpu_col_nodes_device writes
+ *   DAH tree   offset *dah_off, (8k - 1) * 32 B per square: the RFC-6962 tree
+ *              over rowRoots || colRoots (4k leaves, a power of two, so no node
+ *              is promoted); level 0 = the 4k leaf hashes SHA256(0x00 | root90),
+ *              level L packed after level L - 1, so node (L, p) is digest
+ *              8k - (8k >> L) + p and the last digest is the data root
+ * so dagpu_nmt_prove_batch_device, dagpu_nmt_namespace_* and
+ * dagpu_row_nodes_gather_device work unchanged on the slices of square i.
+ * The call only ENQUEUES on `stream`: the shapes are uniform, nothing is
+ * uploaded and nothing is synchronised.  The number of launches does not depend
+ * on n: one leaf pass over all n (2k)^2 cells, level L of the row AND column
+ * trees of all squares in one launch (log2(2k) launches), each DAH level of all
+ * squares in one launch (log2(4k) + 1).  No push-order check: the squares were
+ * extended, and their status words say what that found.  d_workspace
+ * (dagpu_proof_store_workspace_size(k, n) bytes) is reserved.  Sizes are 0 for
+ * an invalid k or n = 0.
+ *
+ * dagpu_nmt_prove_squares_device is dagpu_nmt_prove_batch_device across the
+ * squares of such a store, with one more request word,
+ *   req[5i..] = { square, axis, index, start, end }     (HOST)
+ * the same node rule and output order, the same d_ns_out / d_shares_out
+ * semantics (cells read from d_eds + square * square_stride) and the same
+ * stream contract (the call returns when the requests are uploaded; the
+ * kernels are only enqueued; d_workspace 16-B aligned,
+ * dagpu_nmt_prove_squares_workspace_size(n_req) bytes).  Per request i it
+ * also emits the merkle half:
+ *   d_axis_roots_out  i x 90 B (2-B aligned): the root of the proven tree, from
+ *                     the store's top level
+ *   d_leaf_hash_out   i x 32 B (16-B aligned): that root's leaf hash in the DAH tree
+ *   d_aunts_out       log2(4k) x 32 B at i * log2(4k) (16-B aligned): the aunts
+ *                     of leaf axis*2k + index, leaf to root, in the order of
+ *                     merkle.ProofsFromByteSlices: at level L node (L, (leaf >> L) ^ 1)
+ *   desc_out          HOST, n_req x DAGPU_NMT_DESC_WORDS as the single-square
+ *                     call with ns_index = i and root_index = i: the roots
+ *                     table of a following dagpu_nmt_verify_batch_device is
+ *                     d_axis_roots_out itself
+ *   mdesc_out         HOST, n_req x DAGPU_MERKLE_DESC_WORDS: { index =
+ *                     axis*2k + index, total = 4k, n_aunts = log2(4k), aunt_off
+ *                     = i * log2(4k), leaf_index = i, root_index = square }:
+ *                     leaves are d_axis_roots_out (leaf_len 90), roots the n_sq
+ *                     data roots (32 B each)
+ * Each of the three merkle outputs and each descriptor array may be NULL.
+ * Nothing is hashed.  A square outside [0, n_sq), axis not 0 / 1, index outside
+ * [0, 2k), not 0 <= start < end <= 2k, more nodes than nodes_cap or (with
+ * d_shares_out) more cells than shares_cap fails the whole call with
+ * DAGPU_ERR_ARG before anything is launched; every output, the host
+ * descriptors and *n_nodes_total stay untouched.
+ *
+ * dagpu_share_proof_requests is NewShareInclusionProof's row split
+ * (pkg/proof/proof.go:63-67, 127-140) as host arithmetic, context-free:
+ * sreq[3i..] = { square, start, end }, a range of row-major ODS share indexes,
+ * 0 <= start < end <= k^2, becomes one 5-word request per touched row (axis 0,
+ * index = row): the first from start % k, the last to (end-1) % k inclusive,
+ * the rows between [0, k).  span_out (n + 1) holds the prefix sums of rows per
+ * range, *n_req the total.  An invalid range or square, or more rows than
+ * `cap`, gives DAGPU_ERR_ARG and writes nothing. */
+#define DAGPU_PROVE_SQ_REQ_WORDS 5
+size_t dagpu_proof_store_size(uint32_t k, size_t n, size_t* col_off, size_t* dah_off);
+size_t dagpu_proof_store_workspace_size(uint32_t k, size_t n);
+int dagpu_proof_store_device(dagpu_ctx* ctx, uint32_t k, size_t n, const uint8_t* d_eds,
+                             size_t square_stride, uint8_t* d_store, void* d_workspace, void* stream);
+size_t dagpu_nmt_prove_squares_workspace_size(size_t n_req);
+int dagpu_nmt_prove_squares_device(dagpu_ctx* ctx, uint32_t k, size_t n_sq, size_t n_req,
+                                   const int64_t* req, const uint8_t* d_eds, size_t square_stride,
+                                   const uint8_t* d_store, uint8_t* d_nodes_out, size_t nodes_cap,
+                                   uint8_t* d_ns_out, uint8_t* d_shares_out, size_t shares_cap,
+                                   uint8_t* d_axis_roots_out, uint8_t* d_leaf_hash_out,
+                                   uint8_t* d_aunts_out, int64_t* desc_out, int64_t* mdesc_out,
+                                   size_t* n_nodes_total, void* d_workspace, void* stream);
+int dagpu_share_proof_requests(uint32_t k, size_t n_sq, size_t n, const int64_t* sreq,
+                               int64_t* req_out, size_t cap, int64_t* span_out, size_t* n_req);
+
 /* ---- Namespace proofs: ProveNamespace / VerifyNamespace -------------------
  * "Every share of namespace N in this square, with a proof that nothing was
  * left out": nmt ProveNamespace, Proof.VerifyNamespace and absence proofs (what
