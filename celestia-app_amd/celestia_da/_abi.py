@@ -119,6 +119,9 @@ EXPORTS = (
     "dagpu_nmt_namespace_workspace_size",
     "dagpu_nmt_namespace_ranges_device",
     "dagpu_nmt_prove_namespace_batch_device",
+    "dagpu_nmt_namespace_squares_workspace_size",
+    "dagpu_nmt_namespace_squares_count_device",
+    "dagpu_nmt_prove_namespace_squares_device",
 )
 
 # d_status bits of dagpu_blob_commitments_device
@@ -138,6 +141,7 @@ MERKLE_DESC_WORDS = 6
 NMT_DESC_WORDS = 8
 NMT_NS_DESC_WORDS = 9
 NS_OUTSIDE, NS_PRESENT, NS_ABSENT = 0, 1, 2
+NS_HIT_WORDS = 6
 
 PREFIX_NONE = 0
 PREFIX_SELF = 1
@@ -318,6 +322,12 @@ def lib() -> ctypes.CDLL:
         L.dagpu_nmt_namespace_ranges_device.argtypes = [vp, ctypes.c_uint32, sz, vp, vp, vp, vp, vp, vp]
         L.dagpu_nmt_prove_namespace_batch_device.argtypes = [vp, ctypes.c_uint32, sz, vp, vp, vp, vp, sz, vp, vp, sz,
                                                              vp, sz, vp, vp, sz, vp, vp, vp]
+        L.dagpu_nmt_namespace_squares_workspace_size.argtypes = [ctypes.c_uint32, sz, sz, sz]
+        L.dagpu_nmt_namespace_squares_workspace_size.restype = sz
+        L.dagpu_nmt_namespace_squares_count_device.argtypes = [vp, ctypes.c_uint32, sz, sz, vp, vp, vp, vp, vp, vp]
+        L.dagpu_nmt_prove_namespace_squares_device.argtypes = [vp, ctypes.c_uint32, sz, sz, vp, vp, sz, vp, vp, sz,
+                                                               vp, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp, sz, vp,
+                                                               vp, vp]
         L.dagpu_profile_enable.argtypes = [vp, ctypes.c_int]
         L.dagpu_profile_read.argtypes = [vp, vp, vp, ctypes.c_int]
         _lib = L

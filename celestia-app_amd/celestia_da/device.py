@@ -378,6 +378,114 @@ def nmt_prove_namespace_batch_device(nodes, namespaces, caps=None, ctx: Optional
             out_lh[:int(counts[1]) * ROOT], desc[:n], pairs[:n], counts)
 
 
+def nmt_namespace_squares_count_device(store: ProofStore, namespaces, per: bool = True,
+                                       ctx: Optional[Context] = None, stream: Optional[torch.cuda.Stream] = None,
+                                       workspace: Optional[torch.Tensor] = None):
+    """dagpu_nmt_namespace_squares_count_device: how many namespace proofs a
+    list of namespaces has over ALL squares of a ProofStore.  Returns (counts,
+    per): counts an int64[4] HOST array (proofs with kind != 0, absence proofs,
+    proof nodes, proven cells), per the (n_q, n_sq) int32 HOST array of proofs
+    per (query, square) -- which squares hold a namespace -- or None with
+    per=False.  Synchronises `stream` once."""
+    import numpy as np
+    c = ctx or store.ctx
+    q = _ns_table(namespaces)
+    n_q, dev = int(q.shape[0]), store.store.device
+    counts = np.zeros(4, np.int64)
+    per_out = np.zeros((n_q, store.n), np.int32) if per else None
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    need = c._L.dagpu_nmt_namespace_squares_workspace_size(store.k, store.n, n_q, 0)
+    if need == 0:
+        raise DAError(_abi.ERR_ARG, f"{n_q} namespaces x {store.n} squares x {store.w} rows overflow")
+    if workspace is None:
+        with torch.cuda.stream(s):
+            workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+    if workspace.numel() < need:
+        raise ValueError("workspace smaller than dagpu_nmt_namespace_squares_workspace_size")
+    rc = c._L.dagpu_nmt_namespace_squares_count_device(
+        c.handle, store.k, store.n, n_q, _abi.addr(q), _abi.addr(store.store), _abi.addr(counts),
+        _abi.addr(per_out) if per and n_q else None, _abi.addr(workspace), _stream_handle(s))
+    if rc != 0:
+        raise DAError(rc, c.last_error())
+    return counts, per_out
+
+
+class NamespaceSquaresProofs(NamedTuple):
+    """What nmt_prove_namespace_squares_device returns: uint8 device tensors
+    (axis_roots, dah_leaf_hashes and aunts None without to_data_root=True) and
+    the HOST arrays."""
+    nodes: torch.Tensor                      # 90 B per proof node
+    namespaces: torch.Tensor                 # 29 B per query
+    shares: torch.Tensor                     # 512 B per proven cell
+    leaf_hashes: torch.Tensor                # 90 B per absence proof
+    axis_roots: Optional[torch.Tensor]       # 90 B per proof: its row root
+    dah_leaf_hashes: Optional[torch.Tensor]  # 32 B per proof
+    aunts: Optional[torch.Tensor]            # log2(4k) x 32 B per proof
+    desc: "object"    # (n, 9) int64: nmt_verify_namespace_batch_device, roots table = axis_roots
+    mdesc: "object"   # (n, 6) int64: dagpu_merkle_verify_batch, roots = store.data_roots(); None without to_data_root
+    hits: "object"    # (n, 6) int32: query, square, row, kind, start, end
+    counts: "object"  # int64[4]: proofs, absence proofs, proof nodes, proven cells
+
+
+def nmt_prove_namespace_squares_device(store: ProofStore, namespaces, caps=None, to_data_root: bool = True,
+                                       ctx: Optional[Context] = None, stream: Optional[torch.cuda.Stream] = None,
+                                       workspace: Optional[torch.Tensor] = None) -> NamespaceSquaresProofs:
+    """dagpu_nmt_prove_namespace_squares_device: nmt ProveNamespace of every
+    namespace of a list on every ROW tree of every square of a ProofStore, in
+    (query, square, row) order, and with to_data_root the merkle proof of each
+    row root under its square's data root; enqueued on `stream`.
+
+    caps = (proofs, nodes, cells, leaf_hashes) sizes the outputs as in
+    nmt_prove_namespace_batch_device; a capacity too small raises
+    DAError(ERR_ARG).  Without caps the need is taken from
+    nmt_namespace_squares_count_device first (a second search)."""
+    import numpy as np
+    c = ctx or store.ctx
+    q = _ns_table(namespaces)
+    n_q, dev = int(q.shape[0]), store.store.device
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    if caps is None:
+        caps = nmt_namespace_squares_count_device(store, q, per=False, ctx=c, stream=s)[0][[0, 2, 3, 1]]
+    n_p, n_nodes, n_cells, n_lh = (int(v) for v in caps)
+    need = c._L.dagpu_nmt_namespace_squares_workspace_size(store.k, store.n, n_q, n_p)
+    if need == 0:
+        raise DAError(_abi.ERR_ARG, f"{n_q} namespaces x {store.n} squares x {store.w} rows overflow")
+    la = store.w.bit_length()  # log2(4k) aunts per proof
+    with torch.cuda.stream(s):
+        if workspace is None:
+            workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+        out_nodes = torch.empty((n_nodes * ROOT,), dtype=torch.uint8, device=dev)
+        out_ns = torch.empty((n_q * 29,), dtype=torch.uint8, device=dev)
+        out_shares = torch.empty((n_cells * 512,), dtype=torch.uint8, device=dev)
+        out_lh = torch.empty((n_lh * ROOT,), dtype=torch.uint8, device=dev)
+        out_roots = torch.empty((n_p * ROOT,), dtype=torch.uint8, device=dev) if to_data_root else None
+        out_dlh = torch.empty((n_p * 32,), dtype=torch.uint8, device=dev) if to_data_root else None
+        out_aunts = torch.empty((n_p * la * 32,), dtype=torch.uint8, device=dev) if to_data_root else None
+    if workspace.numel() < need:
+        raise ValueError("workspace smaller than dagpu_nmt_namespace_squares_workspace_size")
+    desc = np.zeros((n_p, _abi.NMT_NS_DESC_WORDS), np.int64)
+    mdesc = np.zeros((n_p, _abi.MERKLE_DESC_WORDS), np.int64) if to_data_root else None
+    hits = np.zeros((n_p, _abi.NS_HIT_WORDS), np.int32)
+    counts = np.zeros(4, np.int64)
+    rc = c._L.dagpu_nmt_prove_namespace_squares_device(
+        c.handle, store.k, store.n, n_q, _abi.addr(q), _abi.addr(store.eds), store.square_stride,
+        _abi.addr(store.store), _abi.addr(out_nodes) if n_nodes else None, n_nodes,
+        _abi.addr(out_ns) if n_q else None, _abi.addr(out_shares) if n_cells else None, n_cells,
+        _abi.addr(out_lh) if n_lh else None, n_lh,
+        _abi.addr(out_roots) if to_data_root and n_p else None, _abi.addr(out_dlh) if to_data_root and n_p else None,
+        _abi.addr(out_aunts) if to_data_root and n_p else None, _abi.addr(desc) if n_p else None,
+        _abi.addr(mdesc) if to_data_root and n_p else None, _abi.addr(hits) if n_p else None, n_p, _abi.addr(counts),
+        _abi.addr(workspace), _stream_handle(s))
+    if rc != 0:
+        raise DAError(rc, c.last_error())
+    n = int(counts[0])
+    return NamespaceSquaresProofs(
+        out_nodes[:int(counts[2]) * ROOT], out_ns, out_shares[:int(counts[3]) * 512], out_lh[:int(counts[1]) * ROOT],
+        out_roots[:n * ROOT] if to_data_root else None, out_dlh[:n * 32] if to_data_root else None,
+        out_aunts[:n * la * 32] if to_data_root else None, desc[:n], mdesc[:n] if to_data_root else None, hits[:n],
+        counts)
+
+
 def nmt_verify_namespace_batch_device(desc, namespaces: torch.Tensor, leaves: torch.Tensor, leaf_len: int,
                                       nodes: torch.Tensor, leaf_hashes: torch.Tensor, roots: torch.Tensor,
                                       ctx: Optional[Context] = None, stream: Optional[torch.cuda.Stream] = None,
@@ -898,6 +1006,13 @@ class DeviceSquares:
         if rows is not None:
             rec = rec[list(rows)]
         return self.share_proofs([(int(sq), int(a), int(a + c)) for sq, a, c in rec], stream=stream)
+
+    def namespace_proofs(self, namespaces, stream: Optional[torch.cuda.Stream] = None):
+        """proof.prove_namespaces_squares over the cached proof_store():
+        out[q][square] = list of (row, NMTProof, shares, MerkleProof) for every
+        namespace of the list on every square of the batch."""
+        from . import proof as pf
+        return pf.prove_namespaces_squares(self.proof_store(stream), namespaces, stream=stream)
 
     def _ck(self, rc: int) -> None:
         if rc != 0:

@@ -432,6 +432,38 @@ def prove_namespaces(axis_nodes, namespaces: Sequence[bytes]) -> List[List[Tuple
     return out
 
 
+def prove_namespaces_squares(store, namespaces: Sequence[bytes], stream=None):
+    """prove_namespaces for every square of a device.ProofStore at once, and on
+    to the data root: out[q][square] = list of (row, proof, shares, merkle) --
+    the (row, proof, shares) of prove_namespaces(store.square(square), ...) and
+    the MerkleProof of that row's root under the square's data root (leaf = the
+    90-B row root, which proof.nodes fold to).  One
+    dagpu_nmt_prove_namespace_squares_device call and one copy to the host."""
+    import torch
+
+    from .device import nmt_prove_namespace_squares_device
+    out = [[[] for _ in range(store.n)] for _ in namespaces]
+    if not len(namespaces):
+        return out
+    dev = store.store.device
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    r = nmt_prove_namespace_squares_device(store, namespaces, to_data_root=True, stream=s)
+    parts = (r.nodes, r.shares, r.leaf_hashes, r.dah_leaf_hashes, r.aunts)
+    with torch.cuda.stream(s):
+        host = torch.cat(parts).cpu().numpy().tobytes()
+    at = np.cumsum([0] + [t.numel() for t in parts])
+    nodes, shares, hashes, dlh, aunts = (host[at[j]:at[j + 1]] for j in range(len(parts)))
+    la = (2 * store.w).bit_length() - 1
+    for i, (d, (q, sq, row, _, _, _)) in enumerate(zip(r.desc, r.hits)):
+        lh = hashes[90 * int(d[8]):90 * int(d[8]) + 90] if d[8] >= 0 else b""
+        p = NMTProof(int(d[0]), int(d[1]), [nodes[90 * j:90 * (j + 1)] for j in range(int(d[5]), int(d[5] + d[4]))], lh)
+        mp = MerkleProof(2 * store.w, int(row), dlh[32 * i:32 * (i + 1)],
+                         [aunts[32 * (i * la + a):32 * (i * la + a + 1)] for a in range(la)])
+        out[int(q)][int(sq)].append(
+            (int(row), p, [shares[512 * j:512 * (j + 1)] for j in range(int(d[3]), int(d[3] + d[2]))], mp))
+    return out
+
+
 def verify_namespace_data(row_roots: Sequence[bytes], nid: bytes,
                           rows: Sequence[Tuple[int, NMTProof, Sequence[bytes]]],
                           ctx: Optional[Context] = None) -> bool:

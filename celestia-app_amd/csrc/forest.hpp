@@ -181,6 +181,38 @@ hipError_t launch_ns_find(const NsFindArgs& a, hipStream_t s);
 hipError_t launch_ns_leaf_nodes(const uint8_t* row_nodes, const int64_t* rec_index, long n, uint8_t* out,
                                 hipStream_t s);
 
+// The same search across the squares of a batch proof store, with the proofs
+// counted, ordered and laid out on the device (nmt_namespace.hip; arithmetic
+// and workspace carve in ns_squares_layout.hpp).  One lane per (query, square,
+// row); every pointer but queries / store points into the workspace.
+struct NsSqArgs {
+  long n_q, n_sq;
+  int w, logw;              // leaves per row tree (2k) and log2 of it
+  long lanes, pairs;        // n_q * n_sq * w, n_q * n_sq
+  long blocks, chunks;      // blocks of 256 lanes, chunks of 256 blocks
+  const uint8_t* queries;   // n_q namespaces, zero padded to 32 B, 16-B aligned
+  const uint8_t* store;     // the batch proof store: square i's rows at i * row_bytes
+  long row_bytes;
+  uint32_t* words;          // lanes packed ranges (ns_sq_pack)
+  int64_t* bsum;            // blocks x 4 sums
+  int64_t* csum;            // chunks x 4 sums
+  int64_t* totals;          // 4: proofs, absence proofs, proof nodes, proven cells
+  int32_t* per;             // pairs proof counts, or null
+  // written by the scatter, for ProveSqArgs and the host
+  int64_t* req;             // proofs x {prove_pack_req word, square}
+  int64_t* node_off;        // proofs + 1
+  int64_t* leaf_off;        // proofs + 1
+  int64_t* abs_rec;         // absence proofs: level-0 record index in the row region
+  uint32_t* hits;           // proofs x {lane, packed range}
+};
+// find, block sums, the two scan levels and (with a.per) the per-pair counts
+hipError_t launch_ns_sq_search(const NsSqArgs& a, hipStream_t s);
+// after the host has compared a.totals with the capacities
+hipError_t launch_ns_sq_scatter(const NsSqArgs& a, hipStream_t s);
+// launch_ns_leaf_nodes with record indexes counted from the start of the row region
+hipError_t launch_ns_sq_leaf_nodes(const uint8_t* store, const int64_t* rec_index, long n, uint8_t* out,
+                                   hipStream_t s);
+
 // Host-side level plan of one forest.  Leaves (level 0) are either packed tree
 // after tree (ragged: counts[t] leaves each) or uniform with (tstride,
 // lstride) addressing inside a caller-owned leaf array.  Levels >= 1 are packed

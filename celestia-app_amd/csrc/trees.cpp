@@ -35,6 +35,11 @@
 //                          square for a list of namespaces: search on the device
 //                          (nmt_namespace.hip, ns_find.hpp), then the range-proof
 //                          emit and gather kernels
+//   dagpu_nmt_namespace_squares_count_device / dagpu_nmt_prove_namespace_squares_device
+//                          the same for all n squares of a batch proof store and on
+//                          to the data root: one search over every (query, square,
+//                          row), hits counted, ordered and laid out on the device
+//                          (ns_squares_layout.hpp); only the hit records come back
 // Each call uploads the pushes once, hashes every leaf and level of every
 // tree in a handful of launches (nmt_forest.hip) and returns the roots.
 #include <hip/hip_runtime.h>
@@ -51,6 +56,7 @@
 #include "kernels.hpp"
 #include "host_sha256.hpp"
 #include "ns_find.hpp"
+#include "ns_squares_layout.hpp"
 #include "pipe_carve.hpp"
 #include "proof_verify.hpp"
 #include "prove_layout.hpp"
@@ -1109,6 +1115,196 @@ int dagpu_nmt_prove_namespace_batch_device(dagpu_ctx* ctx, uint32_t k, size_t n_
   }
   // the query namespaces, as uploaded for the search (zero padded to 32 B each)
   HIP_TRY(ctx, hipMemcpy2DAsync(d_ns_out, kNsSize, ws, 32, kNsSize, n_q, hipMemcpyDeviceToDevice, s));
+  return DAGPU_OK;
+}
+
+// ---- the same across the squares of a batch proof store (ns_squares_layout.hpp) ----
+
+size_t dagpu_nmt_namespace_squares_workspace_size(uint32_t k, size_t n_sq, size_t n_q, size_t proofs_cap) {
+  NsSqCarve c;
+  if (k == 0 || !is_pow2(k) || k > (uint32_t)kMaxK || !ns_squares_carve(k, n_sq, n_q, proofs_cap, &c)) return 0;
+  return c.total;
+}
+
+namespace {
+
+// Upload the padded queries, search every (query, square, row), count and scan
+// on the device and read the four totals (and per_out) back: one
+// synchronisation.  `a` is left ready for the scatter.
+int ns_sq_search(dagpu_ctx* ctx, uint32_t k, size_t n_sq, size_t n_q, const uint8_t* namespaces,
+                 const uint8_t* d_store, const NsSqCarve& c, size_t row_bytes, int64_t totals[4], int32_t* per_out,
+                 uint8_t* ws, hipStream_t s, NsSqArgs* args) {
+  std::vector<uint8_t> padded(32 * n_q, 0);
+  for (size_t q = 0; q < n_q; q++) memcpy(&padded[32 * q], namespaces + q * kNsSize, kNsSize);
+  NsSqArgs a{};
+  a.n_q = (long)n_q;
+  a.n_sq = (long)n_sq;
+  a.w = (int)(2 * k);
+  a.logw = prove_log2(2 * k);
+  a.lanes = (long)c.lanes;
+  a.pairs = (long)c.pairs;
+  a.blocks = (long)c.blocks;
+  a.chunks = (long)c.chunks;
+  a.queries = ws + c.queries;
+  a.store = d_store;
+  a.row_bytes = (long)row_bytes;
+  a.words = (uint32_t*)(ws + c.words);
+  a.bsum = (int64_t*)(ws + c.bsum);
+  a.csum = (int64_t*)(ws + c.csum);
+  a.totals = (int64_t*)(ws + c.totals);
+  a.per = per_out ? (int32_t*)(ws + c.per) : nullptr;
+  a.req = (int64_t*)(ws + c.req);
+  a.node_off = (int64_t*)(ws + c.node_off);
+  a.leaf_off = (int64_t*)(ws + c.leaf_off);
+  a.abs_rec = (int64_t*)(ws + c.abs_rec);
+  a.hits = (uint32_t*)(ws + c.hits);
+  *args = a;
+  int64_t got[kNsSqSums];
+  std::vector<int32_t> per(per_out ? c.pairs : 0);
+  hipError_t e = hipMemcpyAsync(ws + c.queries, padded.data(), padded.size(), hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = launch_ns_sq_search(a, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(got, a.totals, sizeof got, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess && per_out)
+    e = hipMemcpyAsync(per.data(), a.per, per.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+  const hipError_t e2 = hipStreamSynchronize(s);  // `padded` is read by the upload: always wait
+  HIP_TRY(ctx, e);
+  HIP_TRY(ctx, e2);
+  // what the device reports is checked before anything is sized from it
+  bool ok = ns_sq_totals_ok(got, c.lanes, a.logw, (uint32_t)a.w);
+  int64_t per_sum = 0;
+  for (size_t i = 0; ok && i < per.size(); i++) {
+    ok = per[i] >= 0 && per[i] <= a.w;
+    per_sum += per[i];
+  }
+  if (!ok || (per_out && per_sum != got[0]))
+    return set_err(ctx, DAGPU_ERR_DEVICE, "namespace search returned counts outside the batch");
+  memcpy(totals, got, sizeof got);
+  if (per_out) memcpy(per_out, per.data(), per.size() * sizeof(int32_t));
+  return DAGPU_OK;
+}
+
+int ns_sq_common_check(dagpu_ctx* ctx, const std::string& who, uint32_t k, size_t n_sq, size_t n_q, size_t proofs_cap,
+                       const void* namespaces, const void* d_store, const void* d_workspace, NsSqCarve* c,
+                       ProofStoreLayout* l) {
+  if (n_sq == 0) return set_err(ctx, DAGPU_ERR_ARG, who + ": no squares");
+  if (!proof_store_layout(k, n_sq, l) || !ns_squares_carve(k, n_sq, n_q, proofs_cap, c))
+    return set_err(ctx, DAGPU_ERR_ARG, who + ": the (query, square, row) count or a size overflows");
+  if (!namespaces || !d_store || !d_workspace) return set_err(ctx, DAGPU_ERR_ARG, who + ": null buffer");
+  if ((((uintptr_t)d_workspace | (uintptr_t)d_store) & 15) != 0)
+    return set_err(ctx, DAGPU_ERR_ARG, who + ": misaligned buffer");
+  return DAGPU_OK;
+}
+
+}  // namespace
+
+int dagpu_nmt_namespace_squares_count_device(dagpu_ctx* ctx, uint32_t k, size_t n_sq, size_t n_q,
+                                             const uint8_t* namespaces, const uint8_t* d_store, int64_t* counts_out,
+                                             int32_t* per_out, void* d_workspace, void* stream) {
+  if (!ctx) return DAGPU_ERR_ARG;
+  int rc = check_k(ctx, k);
+  if (rc) return rc;
+  const std::string who = "dagpu_nmt_namespace_squares_count_device";
+  if (n_sq == 0) return set_err(ctx, DAGPU_ERR_ARG, who + ": no squares");
+  if (n_q == 0) {
+    if (counts_out) counts_out[0] = counts_out[1] = counts_out[2] = counts_out[3] = 0;
+    return DAGPU_OK;
+  }
+  if (!counts_out) return set_err(ctx, DAGPU_ERR_ARG, who + ": null buffer");
+  NsSqCarve c;
+  ProofStoreLayout l;
+  rc = ns_sq_common_check(ctx, who, k, n_sq, n_q, 0, namespaces, d_store, d_workspace, &c, &l);
+  if (rc) return rc;
+  NsSqArgs a;
+  return ns_sq_search(ctx, k, n_sq, n_q, namespaces, d_store, c, l.row_bytes, counts_out, per_out,
+                      (uint8_t*)d_workspace, (hipStream_t)stream, &a);
+}
+
+int dagpu_nmt_prove_namespace_squares_device(dagpu_ctx* ctx, uint32_t k, size_t n_sq, size_t n_q,
+                                             const uint8_t* namespaces, const uint8_t* d_eds, size_t square_stride,
+                                             const uint8_t* d_store, uint8_t* d_nodes_out, size_t nodes_cap,
+                                             uint8_t* d_ns_out, uint8_t* d_shares_out, size_t shares_cap,
+                                             uint8_t* d_leaf_hashes_out, size_t leaf_hashes_cap,
+                                             uint8_t* d_axis_roots_out, uint8_t* d_dah_leaf_hash_out,
+                                             uint8_t* d_aunts_out, int64_t* desc_out, int64_t* mdesc_out,
+                                             int32_t* hits_out, size_t proofs_cap, int64_t* counts_out,
+                                             void* d_workspace, void* stream) {
+  if (!ctx) return DAGPU_ERR_ARG;
+  int rc = check_k(ctx, k);
+  if (rc) return rc;
+  const std::string who = "dagpu_nmt_prove_namespace_squares_device";
+  if (n_sq == 0) return set_err(ctx, DAGPU_ERR_ARG, who + ": no squares");
+  if (n_q == 0) {
+    if (counts_out) counts_out[0] = counts_out[1] = counts_out[2] = counts_out[3] = 0;
+    return DAGPU_OK;
+  }
+  if (!counts_out || !d_ns_out || !d_eds || (nodes_cap && !d_nodes_out) || (shares_cap && !d_shares_out) ||
+      (leaf_hashes_cap && !d_leaf_hashes_out) || (proofs_cap && (!desc_out || !hits_out)))
+    return set_err(ctx, DAGPU_ERR_ARG, who + ": null buffer");
+  NsSqCarve c;
+  ProofStoreLayout l;
+  rc = ns_sq_common_check(ctx, who, k, n_sq, n_q, proofs_cap, namespaces, d_store, d_workspace, &c, &l);
+  if (rc) return rc;
+  if ((((uintptr_t)d_eds | (uintptr_t)d_shares_out | (uintptr_t)d_dah_leaf_hash_out | (uintptr_t)d_aunts_out |
+        square_stride) & 15) != 0 ||
+      ((((uintptr_t)d_nodes_out) | (uintptr_t)d_leaf_hashes_out | (uintptr_t)d_axis_roots_out) & 1) != 0)
+    return set_err(ctx, DAGPU_ERR_ARG, who + ": misaligned buffer");
+  const size_t w = 2 * (size_t)k;
+  if (square_stride < w * w * kShareSize)
+    return set_err(ctx, DAGPU_ERR_ARG, who + ": square_stride smaller than a square");
+  hipStream_t s = (hipStream_t)stream;
+  uint8_t* ws = (uint8_t*)d_workspace;
+  NsSqArgs f;
+  int64_t need[kNsSqSums];
+  rc = ns_sq_search(ctx, k, n_sq, n_q, namespaces, d_store, c, l.row_bytes, need, nullptr, ws, s, &f);
+  if (rc) return rc;
+  memcpy(counts_out, need, sizeof need);
+  if (ns_sq_short_capacity(need, proofs_cap, leaf_hashes_cap, nodes_cap, shares_cap) >= 0)
+    return set_err(ctx, DAGPU_ERR_ARG, who + ": a capacity is too small (proofs " + std::to_string(need[0]) +
+                                           ", leaf hashes " + std::to_string(need[1]) + ", nodes " +
+                                           std::to_string(need[2]) + ", cells " + std::to_string(need[3]) +
+                                           " needed)");
+  const size_t n = (size_t)need[0];
+  if (n) {
+    // the tables of the emit kernels are written on the device; only the hit
+    // records come back, and they are re-checked before anything is emitted
+    std::vector<uint32_t> rec(n * kNsHitRecWords);
+    std::vector<int32_t> hits(n * kNsHitWords);
+    HIP_TRY(ctx, launch_ns_sq_scatter(f, s));
+    HIP_TRY(ctx, hipMemcpyAsync(rec.data(), f.hits, rec.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    if (!ns_sq_check_hits(n, rec.data(), n_q, n_sq, (uint32_t)w, need, hits.data()))
+      return set_err(ctx, DAGPU_ERR_DEVICE, "namespace search returned a hit outside the batch");
+    ProveSqArgs a{};
+    a.n = (long)n;
+    a.w = (int)w;
+    a.logw = f.logw;
+    a.req = f.req;
+    a.node_off = f.node_off;
+    a.leaf_off = f.leaf_off;
+    a.n_nodes = (long)need[2];
+    a.n_leaves = (long)need[3];
+    a.store = d_store;
+    a.row_bytes = (long)l.row_bytes;
+    a.col_bytes = (long)l.col_bytes;
+    a.dah_bytes = (long)l.dah_bytes;
+    a.col_off = (long)l.col_off;
+    a.dah_off = (long)l.dah_off;
+    a.eds = d_eds;
+    a.square_stride = (long)square_stride;
+    a.nodes_out = d_nodes_out;
+    a.shares_out = d_shares_out;
+    a.axis_roots_out = d_axis_roots_out;
+    a.leaf_hash_out = d_dah_leaf_hash_out;
+    a.aunts_out = d_aunts_out;
+    HIP_TRY(ctx, launch_prove_sq_emit(a, s));
+    HIP_TRY(ctx, launch_prove_sq_shares(a, s));
+    HIP_TRY(ctx, launch_ns_sq_leaf_nodes(d_store, f.abs_rec, (long)need[1], d_leaf_hashes_out, s));
+    if (d_axis_roots_out || d_dah_leaf_hash_out || d_aunts_out) HIP_TRY(ctx, launch_prove_sq_merkle(a, s));
+    memcpy(hits_out, hits.data(), hits.size() * sizeof(int32_t));
+    ns_sq_fill_desc(k, n, hits.data(), desc_out, mdesc_out);
+  }
+  // the query namespaces, as uploaded for the search (zero padded to 32 B each)
+  HIP_TRY(ctx, hipMemcpy2DAsync(d_ns_out, kNsSize, ws + c.queries, 32, kNsSize, n_q, hipMemcpyDeviceToDevice, s));
   return DAGPU_OK;
 }
 

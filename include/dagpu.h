@@ -737,6 +737,98 @@ int dagpu_nmt_prove_namespace_batch_device(dagpu_ctx* ctx, uint32_t k, size_t n_
                                            int64_t* desc_out, int32_t* pairs_out, size_t proofs_cap,
                                            int64_t* counts_out, void* d_workspace, void* stream);
 
+/* ---- Namespace proofs across the squares of a batch proof store -----------
+ * dagpu_nmt_prove_namespace_squares_device is
+ * dagpu_nmt_prove_namespace_batch_device for all n_sq squares of a
+ * dagpu_proof_store_device store in one call, with the merkle half to the data
+ * root that dagpu_nmt_prove_squares_device emits.  The rules are exactly those
+ * of the block above (row trees only, all 2k rows of every square; nothing new
+ * is recalled from nmt, parity stays unpinned as stated there), and the
+ * single-square call is the specification: the proof of (query, square, row)
+ * is byte for byte what it emits for (query, row) on the slices of that square.
+ *
+ * One search runs over every (query, square, row); the hits are counted,
+ * ordered and laid out on the device, and the emit, share-gather and merkle
+ * kernels read their tables from there.  Proofs with kind != 0 are listed in
+ * (query, square, row) order, ascending.  counts_out[4] (HOST) = { proofs,
+ * absence proofs, proof nodes, proven cells } over the whole batch.
+ *   namespaces        HOST, n_q x 29 B
+ *   d_eds             square i at d_eds + i * square_stride (16-B aligned both;
+ *                     square_stride >= (2k)^2 * 512)
+ *   d_store           the batch proof store of the n_sq squares (16-B aligned)
+ *   d_nodes_out, d_shares_out, d_leaf_hashes_out, d_ns_out
+ *                     as in the single-square call: the proofs' nodes (90 B each,
+ *                     2-B aligned), the cells of presence proofs (512 B each,
+ *                     16-B aligned), the level-0 nodes of absence proofs (90 B,
+ *                     2-B aligned) and the n_q query namespaces (29 B each)
+ *   d_axis_roots_out  i x 90 B (2-B aligned): the row root of proof i
+ *   d_dah_leaf_hash_out  i x 32 B (16-B aligned): its leaf hash in the DAH tree
+ *   d_aunts_out       log2(4k) x 32 B at i * log2(4k) (16-B aligned): the aunts
+ *                     of leaf `row` of 4k, leaf to root
+ *                     -- each of the three may be NULL, as in
+ *                     dagpu_nmt_prove_squares_device
+ *   desc_out          HOST, DAGPU_NMT_NS_DESC_WORDS per proof: ns_index = query,
+ *                     root_index = i (the roots table of a following
+ *                     dagpu_nmt_verify_namespace_batch_device is
+ *                     d_axis_roots_out itself), n_leaves = 0 and
+ *                     leaf_hash_index = running absence count for an absence
+ *                     proof, -1 otherwise
+ *   mdesc_out         HOST, may be NULL: DAGPU_MERKLE_DESC_WORDS per proof,
+ *                     { row, 4k, log2(4k), i * log2(4k), i, square }: leaves are
+ *                     d_axis_roots_out (leaf_len 90), roots the n_sq data roots
+ *   hits_out          HOST, DAGPU_NS_HIT_WORDS int32 per proof:
+ *                     { query, square, row, kind, start, end }
+ * A dagpu_nmt_verify_namespace_batch_device and a dagpu_merkle_verify_batch
+ * may follow with no synchronisation beyond what the call itself did.
+ *
+ * dagpu_nmt_namespace_squares_count_device runs the search and the count
+ * alone: counts_out as above and, when per_out (HOST, n_q x n_sq int32, query
+ * major) is not NULL, the proofs of every (query, square): which squares hold
+ * a namespace.
+ *
+ * Cost: the number of launches depends on neither n_sq nor n_q.  The proof
+ * call synchronises `stream` at most twice (after the count, to size the
+ * outputs against the capacities; after the hit records are read back and
+ * before the emit kernels are enqueued), the count call once.  Nothing but the
+ * padded query namespaces is uploaded.  Host work and PCIe traffic are
+ * O(n_q + proofs), for per_out O(n_q * n_sq), never O(n_q * n_sq * 2k).  What
+ * comes back from the device, the four totals and every hit record, is
+ * re-checked on the host before anything is sized or emitted from it; a
+ * violation returns DAGPU_ERR_DEVICE.  The tables the emit kernels read are
+ * written on the device by the same lanes as the hit records and are not read
+ * back: the re-check does not cover them.
+ *
+ * d_workspace (16-B aligned): dagpu_nmt_namespace_squares_workspace_size(k,
+ * n_sq, n_q, proofs_cap) bytes, proofs_cap = 0 for the count call: 4 B per
+ * (query, square, row), 32 B per 256 of them, and 48 B per proof of
+ * proofs_cap.  The size is 0 for an invalid k, n_sq = 0 or a count that
+ * overflows (n_q * n_sq * 2k must stay below 2^31 - 256).
+ *
+ * DAGPU_ERR_ARG before any launch: an invalid k, n_sq = 0, a null or
+ * misaligned buffer, a square_stride smaller than a square, a (query, square,
+ * row) count or a size that overflows.  When a capacity (proofs_cap,
+ * leaf_hashes_cap, nodes_cap, shares_cap) is too small the call returns
+ * DAGPU_ERR_ARG, counts_out holds the need and every other output, the host
+ * arrays included, is untouched.  n_q = 0 is DAGPU_OK: counts_out = 0, nothing
+ * else written.  A batch in which nothing hits is DAGPU_OK with zero counts;
+ * only d_ns_out is written. */
+#define DAGPU_NS_HIT_WORDS 6
+size_t dagpu_nmt_namespace_squares_workspace_size(uint32_t k, size_t n_sq, size_t n_q, size_t proofs_cap);
+int dagpu_nmt_namespace_squares_count_device(dagpu_ctx* ctx, uint32_t k, size_t n_sq, size_t n_q,
+                                             const uint8_t* namespaces, const uint8_t* d_store,
+                                             int64_t* counts_out, int32_t* per_out, void* d_workspace,
+                                             void* stream);
+int dagpu_nmt_prove_namespace_squares_device(dagpu_ctx* ctx, uint32_t k, size_t n_sq, size_t n_q,
+                                             const uint8_t* namespaces, const uint8_t* d_eds,
+                                             size_t square_stride, const uint8_t* d_store,
+                                             uint8_t* d_nodes_out, size_t nodes_cap, uint8_t* d_ns_out,
+                                             uint8_t* d_shares_out, size_t shares_cap,
+                                             uint8_t* d_leaf_hashes_out, size_t leaf_hashes_cap,
+                                             uint8_t* d_axis_roots_out, uint8_t* d_dah_leaf_hash_out,
+                                             uint8_t* d_aunts_out, int64_t* desc_out, int64_t* mdesc_out,
+                                             int32_t* hits_out, size_t proofs_cap, int64_t* counts_out,
+                                             void* d_workspace, void* stream);
+
 /* ---- Square construction (host; pkg/square, app version 1) ---------------
  * square.Construct (pkg/square/square.go:22-63, builder.go): ntx txs packed
  * back to back in `txs` (tx_lens[i] bytes each; blob txs in the BlobTx proto
