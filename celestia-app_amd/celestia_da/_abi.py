@@ -82,6 +82,12 @@ EXPORTS = (
     "dagpu_square_read_workspace_size",
     "dagpu_square_read_device",
     "dagpu_compact_units",
+    "dagpu_square_units_workspace_size",
+    "dagpu_square_units_device",
+    "dagpu_square_units_host",
+    "dagpu_square_units_emulate_host",
+    "dagpu_square_read_units_workspace_size",
+    "dagpu_square_read_units_device",
     "dagpu_profile_enable",
     "dagpu_profile_read",
     "dagpu_profile_stages",
@@ -134,6 +140,11 @@ SCAN_SUMMARY_WORDS = 8
 SEQ_SPARSE, SEQ_TX, SEQ_PFB, SEQ_PADDING, SEQ_VERSION_SHIFT = 1, 2, 4, 8, 8
 SEQ_RECORD_BYTES = 64
 READ_BLOBS, READ_COMPACT = 1, 2
+# dagpu_square_units_device / dagpu_square_read_units_device
+UNITS_OK, UNITS_SCAN, UNITS_HOST, UNITS_OVERFLOW = 0, 1, 2, 3
+UNITS_SUMMARY_WORDS = 8
+UNIT_RECORD_BYTES = 32
+READ_UNITS_OVERFLOW, READ_UNITS_INVALID = 1, 2
 
 PROVE_REQ_WORDS = 4
 PROVE_SQ_REQ_WORDS = 5
@@ -267,6 +278,15 @@ def lib() -> ctypes.CDLL:
         L.dagpu_square_read_device.argtypes = [vp, u32, sz, vp, sz, sz, u32, vp, vp, vp, sz, u32, vp, vp, vp, vp, sz,
                                                vp, vp]
         L.dagpu_compact_units.argtypes = [vp, sz, u32, vp, vp, sz, ctypes.POINTER(sz)]
+        L.dagpu_square_units_workspace_size.argtypes = [u32, sz]
+        L.dagpu_square_units_workspace_size.restype = sz
+        L.dagpu_square_units_device.argtypes = [vp, u32, sz, vp, sz, sz, u32, vp, vp, u32, vp, vp, vp, vp, vp]
+        L.dagpu_square_units_host.argtypes = [u32, sz, vp, sz, sz, u32, vp, vp, u32, vp, vp]
+        L.dagpu_square_units_emulate_host.argtypes = [u32, sz, vp, sz, sz, u32, vp, vp, u32, vp, vp]
+        L.dagpu_square_read_units_workspace_size.argtypes = [sz]
+        L.dagpu_square_read_units_workspace_size.restype = sz
+        L.dagpu_square_read_units_device.argtypes = [vp, u32, sz, vp, sz, sz, u32, vp, u32, vp, vp, vp, sz, vp, vp, vp,
+                                                     sz, vp, vp]
         L.dagpu_repair_batch_device_ex.argtypes = [vp, ctypes.c_uint32, sz, vp, vp, vp, vp, vp, vp,
                                                    vp, vp]
         L.dagpu_repair_start.argtypes = [vp, ctypes.c_uint32, sz, vp, vp, vp, vp, vp, vp, vp,

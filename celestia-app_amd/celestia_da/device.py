@@ -698,6 +698,78 @@ def read_sequences_device(k: int, squares: torch.Tensor, square_stride: int, row
     return selected, offsets, totals, payload
 
 
+def unit_table_device(k: int, squares: torch.Tensor, square_stride: int, row_pitch: int, records: torch.Tensor,
+                      summary: torch.Tensor, unit_cap: int, ctx: Optional[Context] = None,
+                      stream: Optional[torch.cuda.Stream] = None, summary_host: bool = True,
+                      workspace: Optional[torch.Tensor] = None):
+    """dagpu_square_units_device over a scan's records and summary (both on the
+    device): where every tx and wrapped PFB of the squares lies.  Returns
+    (units, unit_summary, host): units an (n, unit_cap, 32) uint8 cuda tensor of
+    dagpu_unit_record (square.unit_dtype()), unit_summary (n, 8) int32 on the
+    device, host its copy as a numpy array, for which the call waits, or None
+    with summary_host=False, when everything is only enqueued on `stream`
+    (`workspace`, dagpu_square_units_workspace_size bytes, is allocated when
+    not given).  Records past a square's unit count keep what torch.empty left."""
+    import numpy as np
+    c = ctx or default_context()
+    n, dev = _squares_held(k, squares, square_stride, row_pitch), squares.device
+    if records.dim() != 3 or records.shape[0] != n or records.shape[2] != _abi.SEQ_RECORD_BYTES \
+            or not records.is_contiguous() or records.dtype != torch.uint8:
+        raise ValueError("records must be the (n, seq_cap, 64) uint8 tensor of scan_squares_device")
+    cap, seq_cap = int(unit_cap), int(records.shape[1])
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.stream(s):
+        units = torch.empty((n, max(cap, 1), _abi.UNIT_RECORD_BYTES), dtype=torch.uint8, device=dev)
+        unit_summary = torch.empty((n, _abi.UNITS_SUMMARY_WORDS), dtype=torch.int32, device=dev)
+        ws = workspace if workspace is not None else torch.empty(
+            (max(c._L.dagpu_square_units_workspace_size(k, n), 16),), dtype=torch.uint8, device=dev)
+    host = np.zeros((n, _abi.UNITS_SUMMARY_WORDS), np.int32) if summary_host else None
+    rc = c._L.dagpu_square_units_device(c.handle, k, n, _abi.addr(squares), square_stride, row_pitch, seq_cap,
+                                        _abi.addr(records), _abi.addr(summary), cap, _abi.addr(units),
+                                        _abi.addr(unit_summary), _abi.addr(host), _abi.addr(ws), _stream_handle(s))
+    if rc != 0:
+        raise DAError(rc, c.last_error())
+    return units[:, :cap], unit_summary, host
+
+
+def read_units_device(k: int, squares: torch.Tensor, square_stride: int, row_pitch: int, records: torch.Tensor,
+                      units: torch.Tensor, unit_summary: torch.Tensor, pairs, payload_cap: int,
+                      ctx: Optional[Context] = None, stream: Optional[torch.cuda.Stream] = None,
+                      payload: Optional[torch.Tensor] = None):
+    """dagpu_square_read_units_device: the data bytes of the units `pairs`
+    ((m, 2) of {square, unit index}, on the host) names in unit_table_device's
+    table, gathered into a cuda uint8 tensor of payload_cap bytes (`payload`,
+    when given, is written in place).  Returns (offsets (m,) int64, totals (3,)
+    int64 {m, payload_bytes, flags}, payload), all on the device and only
+    enqueued on `stream`.  flags: _abi.READ_UNITS_OVERFLOW, and
+    _abi.READ_UNITS_INVALID for a pair that names no unit of a square whose
+    code is UNITS_OK (it yields length 0; the unit summary is on the device, so
+    the library cannot refuse it up front)."""
+    import numpy as np
+    c = ctx or default_context()
+    n, dev = _squares_held(k, squares, square_stride, row_pitch), squares.device
+    pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.uint32).reshape(-1, 2))
+    m = len(pairs)
+    if units.dim() != 3 or units.shape[0] != n or units.shape[2] != _abi.UNIT_RECORD_BYTES \
+            or not units.is_contiguous() or units.dtype != torch.uint8:
+        raise ValueError("units must be the contiguous (n, unit_cap, 32) uint8 tensor of unit_table_device")
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.stream(s):
+        offsets = torch.empty((max(m, 1),), dtype=torch.int64, device=dev)
+        totals = torch.empty((3,), dtype=torch.int64, device=dev)
+        if payload is None:
+            payload = torch.empty((max(int(payload_cap), 16),), dtype=torch.uint8, device=dev)
+        ws = torch.empty((max(c._L.dagpu_square_read_units_workspace_size(m), 16),), dtype=torch.uint8, device=dev)
+    rc = c._L.dagpu_square_read_units_device(c.handle, k, n, _abi.addr(squares), square_stride, row_pitch,
+                                             int(records.shape[1]), _abi.addr(records), int(units.shape[1]),
+                                             _abi.addr(units), _abi.addr(unit_summary), _abi.addr(pairs) if m else None,
+                                             m, _abi.addr(offsets), _abi.addr(totals), _abi.addr(payload),
+                                             int(payload_cap), _abi.addr(ws), _stream_handle(s))
+    if rc != 0:
+        raise DAError(rc, c.last_error())
+    return offsets[:m], totals, payload
+
+
 class DeviceSquares:
     """n squares of width k resident on one GPU.
 
@@ -732,8 +804,9 @@ class DeviceSquares:
         self._src_lens = None
         # scan(): (records, summary, host summary, (buffer, square_stride, row_pitch))
         self._scan = None
-        # proof_store(): the ProofStore of self.eds, until the squares change
-        self._proof_store = None
+        # proof_store(): the ProofStore of self.eds, until the squares change;
+        # tx_table(): the unit table of the squares, for as long
+        self._proof_store = self._tx_index = None
 
     def q0(self) -> torch.Tensor:
         """(n, k, k*512) view of Q0 inside the EDS buffer."""
@@ -743,7 +816,7 @@ class DeviceSquares:
     def load_ods(self, ods) -> None:
         """Copy n ODS (anything viewable as (n, k*k*512) uint8) to where extend()
         reads them: self.ods, or Q0 of the EDS when in_place."""
-        self._proof_store = None
+        self._proof_store = self._tx_index = None
         src = ods if isinstance(ods, torch.Tensor) else torch.from_numpy(ods)
         src = src.reshape(self.n, self.k, self.k * 512)
         if self.in_place:
@@ -765,7 +838,7 @@ class DeviceSquares:
         from . import square as sq
         if len(blocks) != self.n:
             raise ValueError(f"{self.n} blocks expected, got {len(blocks)}")
-        self._proof_store = None
+        self._proof_store = self._tx_index = None
         if self.ods is None and not self.in_place:
             raise ValueError("no ODS buffer: DeviceSquares(with_ods=False) takes its input through extend_from")
         m = sq.SQUARE_SIZE_UPPER_BOUND if max_square_size is None else max_square_size
@@ -941,6 +1014,129 @@ class DeviceSquares:
         return [p.deconstruct(pfb_blob_sizes)
                 for p in self._parsed(_abi.READ_BLOBS | _abi.READ_COMPACT, None, stream, from_eds)]
 
+    # ---- tx index (dagpu_square_units_device / dagpu_square_read_units_device) ----
+
+    def tx_table(self, stream: Optional[torch.cuda.Stream] = None, from_eds: Optional[bool] = None):
+        """Where every tx and wrapped PFB of every square lies: scan(), then
+        dagpu_square_units_device over its records; kept until the squares
+        change.  Returns (units, summary): units an (n, top) host array of
+        square.unit_dtype(), row i holding square i's summary[i, 2] units in
+        block tx order (txs, then PFBs: the index NewTxInclusionProof takes),
+        zero past them; summary the (n, 8) int32 unit summaries.  A square the
+        device hands to the host (UNITS_HOST) is downloaded and answered by the
+        host executor, dagpu_square_units_host, which raises ShareError with the
+        reference's message where parse_txs fails; its summary row is then the
+        host executor's.  A square with a scan error raises as scan() does."""
+        import numpy as np
+
+        from . import square as sq
+        if self._tx_index is not None and self._tx_index["from_eds"] == bool(from_eds):
+            return self._tx_index["units"], self._tx_index["summary"]
+        scan = self.scan(stream=stream, from_eds=from_eds)
+        records, summary, _, where = self._scan
+        s = stream if stream is not None else torch.cuda.current_stream(self.eds.device)
+        # a unit takes two bytes at least; four to a share is far above what blocks hold: a
+        # square with more overflows and is indexed again at its true count
+        cap = max(1, int(np.minimum(scan[:, 6] // 2 + 1, 4 * (scan[:, 6] // 474 + 1)).max()))
+        d_units, d_summary, host = unit_table_device(self.k, where[0], where[1], where[2], records, summary, cap,
+                                                     ctx=self.ctx, stream=s)
+        over = host[:, 0] == _abi.UNITS_OVERFLOW
+        if over.any():
+            cap = int(host[over, 1].max())
+            d_units, d_summary, host = unit_table_device(self.k, where[0], where[1], where[2], records, summary, cap,
+                                                         ctx=self.ctx, stream=s)
+        d_units, d_summary, host = d_units[:self.n].contiguous(), d_summary[:self.n], host[:self.n].copy()
+        top = max(1, int(host[:, 2].max()))
+        with torch.cuda.stream(s):
+            units = np.ascontiguousarray(d_units[:, :top].cpu().numpy()).view(sq.unit_dtype()).reshape(self.n, top)
+        units = units.copy()
+        on_host = {}
+        for i in np.nonzero(host[:, 0] == _abi.UNITS_HOST)[0]:
+            i = int(i)
+            buf, stride, pitch = where
+            with torch.cuda.stream(s):
+                ods = buf[i * stride:i * stride + (self.k - 1) * pitch + self.k * 512].cpu().numpy()
+                rec = records[i].cpu().numpy().view(sq.seq_dtype()).reshape(-1)
+            u, sm = sq.units_native(ods, self.k, records=rec, scan=scan[i], row_pitch=pitch)
+            if len(u) > units.shape[1]:
+                units = np.concatenate([units, np.zeros((self.n, len(u) - units.shape[1]), units.dtype)], axis=1)
+            units[i] = 0
+            units[i, :len(u)] = u
+            host[i] = sm
+            on_host[i] = (ods, rec, pitch)
+        for i in range(self.n):
+            units[i, int(host[i, 2]):] = 0
+        self._tx_index = {"from_eds": bool(from_eds), "units": units, "summary": host, "d_units": d_units,
+                          "d_summary": d_summary, "on_host": on_host, "records": records, "where": where}
+        return units, host
+
+    def tx_ranges(self, stream: Optional[torch.cuda.Stream] = None, from_eds: Optional[bool] = None):
+        """Per square the list of (start, end) share ranges of its units in
+        block tx order: Builder.FindTxShareRange of every tx index."""
+        units, summary = self.tx_table(stream, from_eds)
+        return [[(int(u["start_share"]), int(u["end_share"])) for u in units[i, :int(summary[i, 2])]]
+                for i in range(self.n)]
+
+    def _tx_units(self, pairs, stream, from_eds=None):
+        """The table's records of (square, tx index) pairs, checked as NewTxInclusionProof checks the index."""
+        units, summary = self.tx_table(stream, from_eds)
+        pairs = [(int(a), int(b)) for a, b in pairs]
+        for i, t in pairs:
+            if not 0 <= i < self.n:
+                raise ValueError(f"square {i} of {self.n}")
+            if not 0 <= t < int(summary[i, 2]):
+                raise DAError(_abi.ERR_ARG, f"txIndex {t} out of bounds")
+        return pairs, [units[i, t] for i, t in pairs]
+
+    def read_tx_units(self, pairs, stream: Optional[torch.cuda.Stream] = None, from_eds: Optional[bool] = None):
+        """The bytes of the txs named by (square, tx index) pairs, a PFB as its
+        wrapped IndexWrapper bytes (what shares.parse_txs returns): gathered in
+        HBM straight from the table (dagpu_square_read_units_device), one
+        download of just those bytes.  The host holds the unit summaries, so an
+        index past a square's units raises DAError(ERR_ARG, "txIndex N out of
+        bounds") before anything runs; units of a square the host executor
+        answered are cut from that square's download."""
+        import numpy as np
+
+        from . import square as sq
+        pairs, recs = self._tx_units(pairs, stream, from_eds)
+        ix = self._tx_index
+        out = [None] * len(pairs)
+        dev = [j for j, (i, _) in enumerate(pairs) if i not in ix["on_host"]]
+        for j, (i, _) in enumerate(pairs):
+            if i in ix["on_host"]:
+                ods, rec, pitch = ix["on_host"][i]
+                out[j] = sq.unit_bytes(ods, self.k, pitch, rec, recs[j])
+        if dev:
+            records, where = ix["records"], ix["where"]
+            need = sum((int(recs[j]["len"]) + 15) & ~15 for j in dev)
+            s = stream if stream is not None else torch.cuda.current_stream(self.eds.device)
+            offsets, totals, payload = read_units_device(
+                self.k, where[0], where[1], where[2], records, ix["d_units"], ix["d_summary"],
+                [pairs[j] for j in dev], need, ctx=self.ctx, stream=s)
+            with torch.cuda.stream(s):
+                flat = torch.cat([totals.view(torch.uint8), offsets.view(torch.uint8), payload[:need]]).cpu().numpy()
+            m = len(dev)
+            tot, offs, data = flat[:24].view(np.int64), flat[24:24 + 8 * m].view(np.int64), flat[24 + 8 * m:]
+            assert int(tot[2]) == 0 and int(tot[1]) == need, "the pairs were checked against the summaries"
+            for j, o in zip(dev, offs):
+                out[j] = data[int(o):int(o) + int(recs[j]["len"])].tobytes()
+        return out
+
+    def tx_proofs(self, pairs, stream: Optional[torch.cuda.Stream] = None):
+        """proof.NewTxInclusionProof (pkg/proof/proof.go:23-45) for (square, tx
+        index) pairs spread over the batch: share_proofs over the table's share
+        ranges, in the tx namespace, or the PFB namespace for a PFB; each equals
+        proof.new_tx_inclusion_proof(block's txs, index) field for field.  One
+        produce call and one download for the list; no square is rebuilt.  An
+        index past a square's units raises DAError(ERR_ARG, "txIndex N out of
+        bounds")."""
+        from . import shares as sh
+        pairs, recs = self._tx_units(pairs, stream)
+        ranges = [(i, int(u["start_share"]), int(u["end_share"])) for (i, _), u in zip(pairs, recs)]
+        ns = [sh.PAY_FOR_BLOB_NAMESPACE if int(u["flags"]) & _abi.SEQ_PFB else sh.TX_NAMESPACE for u in recs]
+        return self.share_proofs(ranges, namespaces=ns, stream=stream)
+
     # ---- share proofs to the data root (dagpu_proof_store_device / dagpu_nmt_prove_squares_device) ----
 
     def proof_store(self, stream: Optional[torch.cuda.Stream] = None) -> ProofStore:
@@ -1020,7 +1216,7 @@ class DeviceSquares:
 
     def extend(self, stream: Optional[torch.cuda.Stream] = None) -> None:
         """ODS -> EDS -> roots -> DAH, enqueued on `stream` (no sync)."""
-        self._proof_store = None
+        self._proof_store = self._tx_index = None
         L = self.ctx._L
         self._ck(L.dagpu_extend_batch_device(
             self.ctx.handle, self.k, self.n, _abi.addr(self.ods), _abi.addr(self.eds),
@@ -1035,7 +1231,7 @@ class DeviceSquares:
         if m > self.n or ods.dtype != torch.uint8 or ods.device != self.eds.device \
                 or not ods.is_contiguous() or ods.numel() != m * self.k * self.k * 512:
             raise ValueError("ods must be a contiguous (m <= n, k*k*512) uint8 tensor on this device")
-        self._proof_store = None
+        self._proof_store = self._tx_index = None
         L = self.ctx._L
         self._ck(L.dagpu_extend_batch_device(
             self.ctx.handle, self.k, m, _abi.addr(ods), _abi.addr(self.eds),
@@ -1044,7 +1240,7 @@ class DeviceSquares:
         return m
 
     def extend_rs(self, stream: Optional[torch.cuda.Stream] = None) -> None:
-        self._proof_store = None
+        self._proof_store = self._tx_index = None
         self._ck(self.ctx._L.dagpu_extend_rs_device(
             self.ctx.handle, self.k, self.n, _abi.addr(self.ods), _abi.addr(self.eds),
             _stream_handle(stream)))
@@ -1055,7 +1251,7 @@ class DeviceSquares:
         present: (n, (2k)^2) uint8, updated in place; status: (n,) int32;
         byz (optional): (n, 4) int32 on the device -> failing axis per square
         (dagpu_repair_batch_device_ex)."""
-        self._proof_store = None
+        self._proof_store = self._tx_index = None
         L = self.ctx._L
         if byz is None:
             self._ck(L.dagpu_repair_batch_device(
@@ -1078,7 +1274,7 @@ class DeviceSquares:
         status / workspace as repair() (status and present indexed from
         `first`; workspace sized for `count` squares)."""
         import ctypes
-        self._proof_store = None
+        self._proof_store = self._tx_index = None
         count = self.n - first if count is None else count
         w = 2 * self.k
         h = ctypes.c_uint64(0)
@@ -1099,7 +1295,7 @@ class DeviceSquares:
         (which includes the repair) before it reuses their blocks, whichever
         stream allocated them."""
         js = stream if stream is not None else torch.cuda.current_stream()
-        self._proof_store = None
+        self._proof_store = self._tx_index = None
         try:
             self._ck(self.ctx._L.dagpu_repair_join(self.ctx.handle, handle, int(js.cuda_stream)))
         finally:

@@ -785,6 +785,73 @@ def parse_native(ods, k: Optional[int] = None) -> ParsedSquare:
     return ParsedSquare(k, rec, summary, payload, fetch)
 
 
+def unit_dtype():
+    """numpy dtype of dagpu_unit_record (32 B)."""
+    import numpy as np
+    return np.dtype([("start_share", "<u4"), ("end_share", "<u4"), ("seq", "<u4"), ("flags", "<u4"),
+                     ("offset", "<u8"), ("len", "<u8")])
+
+
+def units_native(ods, k: Optional[int] = None, unit_cap: Optional[int] = None, emulate: bool = False,
+                 records=None, scan=None, row_pitch: Optional[int] = None):
+    """The tx index of one host square (a uint8 array, or a list of shares):
+    (units[:min(n_units, unit_cap)] of unit_dtype(), unit summary (8,) int32).
+    By default the host executor, dagpu_square_units_host: the serial walk,
+    which raises ShareError with the reference's message for a varint that
+    overflows, and ValueError for first reserved bytes outside the share's
+    content.  emulate=True runs the device algorithm as a host loop instead
+    (dagpu_square_units_emulate_host), whose summary may say UNITS_HOST.
+    records / scan: the square's scan when the caller has it (scan_native's)."""
+    import numpy as np
+
+    from . import _abi
+    L = _abi.lib()
+    if not hasattr(ods, "dtype"):
+        ods = np.frombuffer(b"".join(s.to_bytes() if isinstance(s, Share) else bytes(s) for s in ods), np.uint8)
+    ods = np.ascontiguousarray(ods, np.uint8).reshape(-1)
+    if k is None:
+        k = math.isqrt(ods.size // sh.SHARE_SIZE)
+    pitch = k * sh.SHARE_SIZE if row_pitch is None else row_pitch
+    if records is None:
+        _, records, scan = scan_native(ods, k, row_pitch=pitch)
+    records = np.ascontiguousarray(records)
+    scan = np.ascontiguousarray(scan, np.int32)
+    seq_cap = max(len(records), int(scan[3]) if int(scan[0]) == _abi.SCAN_OK else 0)
+    if len(records) < seq_cap:
+        raise ValueError("fewer records than the scan summary counts")
+    if unit_cap is not None:
+        cap = int(unit_cap)
+    else:  # two bytes to a unit at least, of the compact shares' content
+        cap = int(scan[6]) // 2 + 1 if int(scan[0]) == _abi.SCAN_OK else 1
+    units = np.zeros(max(cap, 1), unit_dtype())
+    summary = np.zeros(_abi.UNITS_SUMMARY_WORDS, np.int32)
+    fn = L.dagpu_square_units_emulate_host if emulate else L.dagpu_square_units_host
+    rc = fn(k, 1, _abi.addr(ods), k * pitch, pitch, seq_cap, _abi.addr(records) if len(records) else None,
+            _abi.addr(scan), cap, _abi.addr(units), _abi.addr(summary))
+    if rc != 0:
+        msg = L.dagpu_last_error(None).decode()
+        raise ShareError(msg) if rc == _abi.ERR_SQUARE else ValueError(f"dagpu_square_units_host: status {rc}: {msg}")
+    return units[:min(int(summary[2]), cap)].copy(), summary
+
+
+def unit_bytes(ods, k: int, row_pitch: int, records, unit) -> bytes:
+    """The data bytes of one unit record of a host square: bytes [offset,
+    offset + len) of its sequence's payload."""
+    import numpy as np
+    first = int(records["first"][int(unit["seq"])])
+    a, n = int(unit["offset"]), int(unit["len"])
+    ods = np.asarray(ods, np.uint8).reshape(-1)
+
+    def share(j):
+        s = first + j
+        at = (s // k) * row_pitch + (s % k) * sh.SHARE_SIZE
+        return ods[at + (38 if j == 0 else 34):at + sh.SHARE_SIZE]
+    j0 = 0 if a < 474 else 1 + (a - 474) // 478
+    j1 = 0 if a + n - 1 < 474 else 1 + (a + n - 1 - 474) // 478
+    base = 0 if j0 == 0 else 474 + 478 * (j0 - 1)
+    return np.concatenate([share(j) for j in range(j0, j1 + 1)])[a - base:a - base + n].tobytes()
+
+
 def deconstruct_device(squares, pfb_blob_sizes: Callable[[bytes], Sequence[int]]) -> List[List[bytes]]:
     """square.Deconstruct of every square of a device.DeviceSquares, from where
     it lies in HBM: scan, gather of every blob and both tx streams, download of

@@ -45,6 +45,7 @@
 #include <vector>
 
 #include "runtime.hpp"
+#include "square_geom.hpp"
 #include "square_read.hpp"
 
 static_assert(sizeof(dagpu_seq_record) == sizeof(dagpu::SqrRecord), "dagpu_seq_record is SqrRecord");
@@ -71,28 +72,6 @@ namespace {
 constexpr uint32_t kScanBlock = 1024, kScanWaves = kScanBlock / 64;
 // per-square accumulators of the scan, in the workspace
 enum { kAccErr1, kAccErr2, kAccVer, kAccSeq, kAccBlobs, kAccBlobBytes, kAccCompactBytes, kAccWords = 8 };
-
-struct SqGeom {
-  const uint8_t* squares;
-  uint64_t square_stride, row_pitch;
-  uint32_t log2k, total;  // total = k * k
-};
-
-constexpr size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
-
-__device__ inline const uint8_t* share_at(const SqGeom& g, uint32_t sq, uint32_t s) {
-  const uint32_t row = s >> g.log2k, col = s - (row << g.log2k);
-  return g.squares + sq * g.square_stride + row * g.row_pitch + (uint64_t)col * kSqShare;
-}
-
-// bytes [0, 40) of a share: its address is a multiple of 16
-__device__ inline SqrHead load_head(const uint8_t* share) {
-  const uint4 a = ((const uint4*)share)[0], b = ((const uint4*)share)[1];
-  const uint2 c = *(const uint2*)(share + 32);
-  const uint64_t w[5] = {a.x | (uint64_t)a.y << 32, a.z | (uint64_t)a.w << 32, b.x | (uint64_t)b.y << 32,
-                         b.z | (uint64_t)b.w << 32, c.x | (uint64_t)c.y << 32};
-  return sqr_decode(w);
-}
 
 // What a share knows after the scan inside its workgroup.
 struct Near {
@@ -208,11 +187,6 @@ __device__ inline void close_sequence(const SqGeom& g, uint32_t sq, uint32_t fir
     o[2] = v[2];
     o[3] = v[3];
   }
-}
-
-__device__ inline uint32_t wave_sum(uint32_t v) {
-  for (uint32_t d = 32; d; d >>= 1) v += __shfl_xor(v, d);
-  return v;
 }
 
 }  // namespace
@@ -468,23 +442,6 @@ __global__ __launch_bounds__(256) void square_gather(SqGeom g, const SqrRecord* 
 }
 
 namespace {
-
-// the argument checks the scan and the read share with dagpu_square_write_device
-int check_geometry(dagpu_ctx* ctx, uint32_t k, size_t n, const void* d_squares, size_t square_stride, size_t row_pitch,
-                   const void* d_workspace, SqGeom& g) {
-  if (!is_pow2(k) || k > kSqMaxWidth) return set_err(ctx, DAGPU_ERR_ARG, "square width must be a power of two <= 1024");
-  if (!d_squares) return set_err(ctx, DAGPU_ERR_ARG, "null argument");
-  if (((uintptr_t)d_squares | square_stride | row_pitch | (uintptr_t)d_workspace) & 15)
-    return set_err(ctx, DAGPU_ERR_ARG, "d_squares, square_stride, row_pitch and d_workspace must be multiples of 16");
-  if (row_pitch < (size_t)k * kSS || (n > 1 && square_stride < (size_t)(k - 1) * row_pitch + (size_t)k * kSS))
-    return set_err(ctx, DAGPU_ERR_ARG, "row_pitch below k * 512 or square_stride below one square");
-  if ((uint64_t)n * k * k > ((uint64_t)1 << 32)) return set_err(ctx, DAGPU_ERR_ARG, "more than 2^32 shares in one call");
-  if (n > 65535) return set_err(ctx, DAGPU_ERR_ARG, "more than 65535 squares in one call");
-  uint32_t log2k = 0;
-  while ((1u << log2k) < k) log2k++;
-  g = {(const uint8_t*)d_squares, (uint64_t)square_stride, (uint64_t)row_pitch, log2k, k * k};
-  return DAGPU_OK;
-}
 
 uint32_t scan_wgs(uint32_t k) { return (k * k + kScanBlock - 1) / kScanBlock; }
 

@@ -14,7 +14,9 @@
 //   sqr_stream_pos     where share j's content starts in its sequence's stream
 //   sqr_make_record    one sequence's record and its length check
 //                      (ShareSequence.validSequenceLen, share_sequence.go:54-76)
-//   sqr_gather_lane    one 8-B word of one share's content into the payload
+//   sqr_gather_window  one 8-B word of one share's content into the payload, of
+//                      a window of the sequence's stream
+//   sqr_gather_lane    the same for the whole payload
 //   sqr_scan_square    the host executor: shares.ParseShares(shares, false)
 //                      (parse.go:42-97) of one square, serially
 //   sqr_compact_units  parseRawData (parse_compact_shares.go:47-66)
@@ -140,18 +142,26 @@ DAGPU_SQ_HD inline bool sqr_make_record(const SqrHead& h, uint32_t first, uint32
 // load and one aligned store; the two edge words, which the neighbouring
 // shares' waves also write, go byte by byte.  Nothing outside the sequence's
 // payload_len bytes is written.
-DAGPU_SQ_HD inline void sqr_gather_lane(const uint8_t* share, uint8_t* dst, bool compact, uint32_t j,
-                                        uint32_t payload_len, uint32_t lane) {
+//
+// sqr_gather_window is the general form: of the sequence's stream only the
+// window [w0, w0 + w_len) is wanted, and `dst` (16-B aligned) is where stream
+// position w0 goes; the words are counted from there.  The whole payload is the
+// window [0, payload_len); one unit of a compact sequence is the window
+// [offset, offset + len) (dagpu_square_read_units_device).
+DAGPU_SQ_HD inline void sqr_gather_window(const uint8_t* share, uint8_t* dst, bool compact, uint32_t j, uint32_t w0,
+                                          uint32_t w_len, uint32_t lane) {
   const uint32_t c_len = j == 0 ? (compact ? kSqFirstCompact : kSqFirstSparse)
                                 : (compact ? kSqContCompact : kSqContSparse);
   const uint32_t c_off = kSqShare - c_len;
   const uint32_t pos = sqr_stream_pos(compact, j);
-  if (pos >= payload_len) return;
-  const uint32_t end = pos + (payload_len - pos < c_len ? payload_len - pos : c_len);
-  const uint32_t lo = ((pos >> 3) + lane) << 3;
-  const uint32_t a = lo > pos ? lo : pos, b = lo + 8 < end ? lo + 8 : end;
+  // the share's part of the window, in stream positions
+  const uint32_t from = pos > w0 ? pos : w0, to = pos + c_len < w0 + w_len ? pos + c_len : w0 + w_len;
+  if (from >= to) return;
+  const uint32_t start = from - w0, end = to - w0;  // the same, counted from dst
+  const uint32_t lo = ((start >> 3) + lane) << 3;
+  const uint32_t a = lo > start ? lo : start, b = lo + 8 < end ? lo + 8 : end;
   if (a >= b) return;
-  const uint8_t* src = share + c_off + (a - pos);
+  const uint8_t* src = share + c_off + (a + w0 - pos);
   if (b - a == 8) {
     const uint64_t v = sqw::load8(src);
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -162,6 +172,10 @@ DAGPU_SQ_HD inline void sqr_gather_lane(const uint8_t* share, uint8_t* dst, bool
     return;
   }
   for (uint32_t n = 0; n < b - a; n++) dst[a + n] = src[n];
+}
+DAGPU_SQ_HD inline void sqr_gather_lane(const uint8_t* share, uint8_t* dst, bool compact, uint32_t j,
+                                        uint32_t payload_len, uint32_t lane) {
+  sqr_gather_window(share, dst, compact, j, 0, payload_len, lane);
 }
 
 // shares.ParseShares(shares, false) of one k x k square, rows row_pitch apart:

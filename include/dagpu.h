@@ -975,10 +975,12 @@ int dagpu_square_plan_blobs(const uint8_t* plan, size_t plan_bytes, uint32_t* ou
  * The opposite direction of dagpu_square_write_device: square.Deconstruct
  * (pkg/square/square.go:65-155) split into a scan of the shares
  * (shares.ParseShares, pkg/shares/parse.go:42-97), a gather of the payload that
- * was asked for, and the serial walk over the tx streams (parseRawData,
- * pkg/shares/parse_compact_shares.go:47-66), which stays on the host.  The
- * arithmetic is csrc/square_read.hpp, shared by the host executor and the
- * kernels (csrc/square_read.hip).
+ * was asked for, and the walk over the tx streams (parseRawData,
+ * pkg/shares/parse_compact_shares.go:47-66): dagpu_compact_units walks one
+ * downloaded stream serially on the host; dagpu_square_units_device ("Tx
+ * index" below) walks every stream of a batch where it lies, one lane per
+ * share.  The arithmetic is csrc/square_read.hpp, shared by the host executor
+ * and the kernels (csrc/square_read.hip).
  *
  * Squares are addressed as in dagpu_square_write_device (square i at
  * d_squares + i * square_stride, rows row_pitch apart: the packed ODS batch or
@@ -1099,6 +1101,108 @@ int dagpu_square_read_device(dagpu_ctx* ctx, uint32_t k, size_t n, const uint8_t
                              uint8_t* d_payload, size_t payload_cap, void* d_workspace, void* stream);
 int dagpu_compact_units(const uint8_t* stream, size_t len, uint32_t first_unit, uint64_t* out_off, uint64_t* out_len,
                         size_t cap, size_t* n);
+
+/* ---- Tx index: where unit i of a block lies in a resident square ----------
+ * A unit is what parseRawData yields: a tx in the tx namespace, a wrapped PFB
+ * (IndexWrapper) in the PFB namespace.  Block tx order is every unit of the tx
+ * namespace's sequences in share order, then every unit of the PFB
+ * namespace's: the index Builder.FindTxShareRange (pkg/square/builder.go:268-317)
+ * and NewTxInclusionProof (pkg/proof/proof.go:23-45) take.  The arithmetic is
+ * csrc/square_units.hpp, shared by the host executor, the host loop that
+ * emulates the kernels and the kernels (csrc/square_units.hip); the argument
+ * why one lane per share finds what the serial walk finds stands there.
+ *
+ * dagpu_square_units_device: over the squares, records and summary of
+ * dagpu_square_scan_device (same addressing, same seq_cap), unit j of square i
+ * at d_units[i * unit_cap + j], j < min(n_units, unit_cap):
+ *   start_share, end_share  row-major ODS share indexes, end exclusive: the
+ *                           share that holds the first byte of the unit's
+ *                           length delimiter, and 1 + the share that holds its
+ *                           last data byte (FindTxShareRange of a square the
+ *                           Builder made)
+ *   seq                     the unit's sequence in the square's record table
+ *   flags                   DAGPU_SEQ_TX or DAGPU_SEQ_PFB
+ *   offset, len             the unit's data bytes in its sequence's payload
+ *                           (what dagpu_square_read_device gathers for it), as
+ *                           dagpu_compact_units reports out_off / out_len
+ * Unit summary, 8 int32 per square: {code, index, n_units, n_tx_units,
+ * n_pfb_units, the sum of len rounded up to 16, 0, 0}:
+ *   DAGPU_UNITS_OK        the table is bit for bit the serial walk's
+ *                         (dagpu_square_units_host)
+ *   DAGPU_UNITS_SCAN      the square's scan code is not DAGPU_SCAN_OK; nothing
+ *                         is produced
+ *   DAGPU_UNITS_HOST      the device could not establish that its walk equals
+ *                         the serial one, or the serial walk would report an
+ *                         error; index = the lowest share where this showed.
+ *                         The table is not to be used: run the host executor
+ *                         on that square
+ *   DAGPU_UNITS_OVERFLOW  n_units > unit_cap; index = n_units, the first
+ *                         unit_cap records are written
+ * and words 2 .. 5 are 0 unless the code is OK or OVERFLOW.  No square the
+ * Builder made takes the HOST code.  unit_summary_out (HOST, may be NULL)
+ * receives a copy of the summary and makes the call wait for it; without it,
+ * and with a workspace, the call only enqueues four launches on `stream`.
+ * d_units and d_unit_summary are 16-B aligned.  d_workspace:
+ * dagpu_square_units_workspace_size(k, n) bytes, 16-B aligned; NULL: the
+ * library allocates it and waits.
+ *
+ * dagpu_square_units_host: the host executor, authoritative: the serial walk
+ * (dagpu_compact_units) over each non-padding compact sequence of host squares
+ * and their host records and summary.  Never DAGPU_UNITS_HOST.  The first
+ * square with a sequence the serial walk refuses ends the call: a varint that
+ * overflows 64 bits is DAGPU_ERR_SQUARE, a first reserved value outside {0,
+ * 38 .. 511} DAGPU_ERR_ARG, with dagpu_compact_units' messages; that square's
+ * summary is zeroed, the squares before it are complete.  No context, no device.
+ * dagpu_square_units_emulate_host: the kernels' algorithm as a host loop over
+ * all shares, the same per-lane functions: the same table and summary as
+ * dagpu_square_units_device, DAGPU_UNITS_HOST included.  For tests and for
+ * checking a square without a device.
+ *
+ * dagpu_square_read_units_device: the data bytes of selected units.  pairs:
+ * m HOST pairs {square, unit index} of uint32.  Unit pairs[t] goes to d_payload
+ * at d_offsets[t], a multiple of 16: the sum over the earlier pairs of len
+ * rounded up to 16.  d_totals = {m, payload_bytes, flags}: flags bit 0
+ * (overflow) when a unit would end past payload_cap, which is then not
+ * gathered, the others are; bit 1 (DAGPU_READ_UNITS_INVALID) when a pair's
+ * square is >= n or not DAGPU_UNITS_OK, or its index is not below n_units and
+ * unit_cap.  The summary lives on the device, so such a pair is not refused up
+ * front: it yields length 0.  Nothing outside a unit's len bytes is written.
+ * d_offsets holds m entries, d_totals 3.  d_workspace:
+ * dagpu_square_read_units_workspace_size(m) bytes, 16-B aligned; with it the
+ * call is enqueued on `stream` (two launches, no host round trip between the
+ * table and the gather) and returns once the pairs have left host memory; with
+ * NULL the library allocates it and waits. */
+#define DAGPU_UNITS_OK 0
+#define DAGPU_UNITS_SCAN 1
+#define DAGPU_UNITS_HOST 2
+#define DAGPU_UNITS_OVERFLOW 3
+#define DAGPU_UNITS_SUMMARY_WORDS 8
+#define DAGPU_READ_UNITS_INVALID 2
+typedef struct dagpu_unit_record {
+  uint32_t start_share, end_share, seq, flags;
+  uint64_t offset, len;
+} dagpu_unit_record; /* 32 bytes */
+size_t dagpu_square_units_workspace_size(uint32_t k, size_t n);
+int dagpu_square_units_device(dagpu_ctx* ctx, uint32_t k, size_t n, const uint8_t* d_squares, size_t square_stride,
+                              size_t row_pitch, uint32_t seq_cap, const dagpu_seq_record* d_records,
+                              const int32_t* d_summary, uint32_t unit_cap, dagpu_unit_record* d_units,
+                              int32_t* d_unit_summary, int32_t* unit_summary_out /* HOST, may be NULL */,
+                              void* d_workspace, void* stream);
+int dagpu_square_units_host(uint32_t k, size_t n, const uint8_t* squares, size_t square_stride, size_t row_pitch,
+                            uint32_t seq_cap, const dagpu_seq_record* records, const int32_t* summary,
+                            uint32_t unit_cap, dagpu_unit_record* units, int32_t* unit_summary);
+int dagpu_square_units_emulate_host(uint32_t k, size_t n, const uint8_t* squares, size_t square_stride,
+                                    size_t row_pitch, uint32_t seq_cap, const dagpu_seq_record* records,
+                                    const int32_t* summary, uint32_t unit_cap, dagpu_unit_record* units,
+                                    int32_t* unit_summary);
+size_t dagpu_square_read_units_workspace_size(size_t m);
+int dagpu_square_read_units_device(dagpu_ctx* ctx, uint32_t k, size_t n, const uint8_t* d_squares,
+                                   size_t square_stride, size_t row_pitch, uint32_t seq_cap,
+                                   const dagpu_seq_record* d_records, uint32_t unit_cap,
+                                   const dagpu_unit_record* d_units, const int32_t* d_unit_summary,
+                                   const uint32_t* pairs /* HOST, 2 per unit */, size_t m, uint64_t* d_offsets,
+                                   uint64_t* d_totals, uint8_t* d_payload, size_t payload_cap, void* d_workspace,
+                                   void* stream);
 
 #ifdef __cplusplus
 }
