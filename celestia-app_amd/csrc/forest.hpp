@@ -77,42 +77,25 @@ hipError_t launch_node_to_rec(const uint8_t* nodes, long n, uint8_t* recs, hipSt
 hipError_t launch_node_gather(const uint8_t* nodes, int w, const uint32_t* req, long n, uint8_t* out,
                               hipStream_t s);
 
-// Batched range proofs from the exported trees of one square (nmt_prove.hip).
-// Everything the host validated and laid out (prove_layout.hpp); the kernels
-// check nothing.
+// Batched range proofs from the exported trees of resident squares
+// (nmt_prove.hip).  Everything the host validated and laid out
+// (prove_layout.hpp, share_proof_layout.hpp); the kernels check nothing.
+// Square i's part of a region is at base + i * (bytes per square): the two
+// exports of one square with strides 0 and no square in the requests, or the
+// regions of a batch proof store.
 struct ProveArgs {
   long n;                   // proofs
   int w, logw;              // leaves per tree (2k) and log2 of it
-  const uint64_t* req;      // n packed requests (prove_pack_req)
+  int req_words;            // 8-B words per request: 1 (prove_pack_req) or 2 (that word, square)
+  const int64_t* req;       // n requests
   const int64_t* node_off;  // n + 1 prefix sums: first output node of proof i
   const int64_t* leaf_off;  // n + 1 prefix sums: first output cell of proof i
   long n_nodes, n_leaves;   // node_off[n], leaf_off[n]
-  const uint8_t* row_nodes; // dagpu_row_nodes_device store (96-B records)
-  const uint8_t* col_inner; // dagpu_col_nodes_device store, null without axis-1 requests
-  const uint8_t* eds;       // the square, for the share gather
-  uint8_t* nodes_out;       // n_nodes packed 90-B nodes
-  uint8_t* ns_out;          // n x 29 B
-  uint8_t* shares_out;      // n_leaves x 512 B
-};
-hipError_t launch_prove_emit(const ProveArgs& a, hipStream_t s);
-hipError_t launch_prove_namespaces(const ProveArgs& a, hipStream_t s);
-hipError_t launch_prove_shares(const ProveArgs& a, hipStream_t s);
-
-// The same producer across the squares of a batch proof store, with the
-// merkle half to the data root (dagpu_nmt_prove_squares_device).  Laid out by
-// share_proof_layout.hpp; the kernels check nothing.
-struct ProveSqArgs {
-  long n;                   // proofs
-  int w, logw;              // leaves per tree (2k) and log2 of it
-  const int64_t* req;       // n x {prove_pack_req word, square}
-  const int64_t* node_off;  // n + 1 prefix sums
-  const int64_t* leaf_off;  // n + 1 prefix sums
-  long n_nodes, n_leaves;
-  const uint8_t* store;     // the batch proof store
-  long row_bytes, col_bytes, dah_bytes;  // per square
-  long col_off, dah_off;    // region starts
-  const uint8_t* eds;       // square i at eds + i * square_stride
-  long square_stride;
+  const uint8_t* row_nodes; // dagpu_row_nodes_device stores (96-B records)
+  const uint8_t* col_inner; // dagpu_col_nodes_device stores, null without axis-1 requests
+  const uint8_t* eds;       // the squares, for the share gather
+  const uint8_t* dah;       // the DAH trees of a batch proof store, for the merkle half
+  long row_bytes, col_bytes, square_stride, dah_bytes;  // per square
   uint8_t* nodes_out;       // n_nodes packed 90-B nodes
   uint8_t* ns_out;          // n x 29 B or null
   uint8_t* shares_out;      // n_leaves x 512 B or null
@@ -120,10 +103,10 @@ struct ProveSqArgs {
   uint8_t* leaf_hash_out;   // n x 32 B or null
   uint8_t* aunts_out;       // n x log2(4k) x 32 B or null
 };
-hipError_t launch_prove_sq_emit(const ProveSqArgs& a, hipStream_t s);
-hipError_t launch_prove_sq_namespaces(const ProveSqArgs& a, hipStream_t s);
-hipError_t launch_prove_sq_shares(const ProveSqArgs& a, hipStream_t s);
-hipError_t launch_prove_sq_merkle(const ProveSqArgs& a, hipStream_t s);
+hipError_t launch_prove_emit(const ProveArgs& a, hipStream_t s);
+hipError_t launch_prove_namespaces(const ProveArgs& a, hipStream_t s);
+hipError_t launch_prove_shares(const ProveArgs& a, hipStream_t s);
+hipError_t launch_prove_sq_merkle(const ProveArgs& a, hipStream_t s);  // the three last outputs, from a.dah
 
 // Batch proof store (proof_store.hip): every row-tree and column-tree node
 // and the DAH tree of n squares, each level of all squares in one launch.
@@ -176,10 +159,10 @@ struct NsFindArgs {
   int32_t* ranges;           // n_q x w x {kind, start, end}
 };
 hipError_t launch_ns_find(const NsFindArgs& a, hipStream_t s);
-// Level-0 records rec_index[0 .. n) of the row store as packed 90-B nodes: the
-// leaf hashes of absence proofs.
-hipError_t launch_ns_leaf_nodes(const uint8_t* row_nodes, const int64_t* rec_index, long n, uint8_t* out,
-                                hipStream_t s);
+// Level-0 records rec_index[0 .. n) as packed 90-B nodes, the leaf hashes of
+// absence proofs; indexes count 96-B records from `base`, a row store or the
+// row region of a batch proof store.
+hipError_t launch_ns_leaf_nodes(const uint8_t* base, const int64_t* rec_index, long n, uint8_t* out, hipStream_t s);
 
 // The same search across the squares of a batch proof store, with the proofs
 // counted, ordered and laid out on the device (nmt_namespace.hip; arithmetic
@@ -198,7 +181,7 @@ struct NsSqArgs {
   int64_t* csum;            // chunks x 4 sums
   int64_t* totals;          // 4: proofs, absence proofs, proof nodes, proven cells
   int32_t* per;             // pairs proof counts, or null
-  // written by the scatter, for ProveSqArgs and the host
+  // written by the scatter, for ProveArgs (two-word requests) and the host
   int64_t* req;             // proofs x {prove_pack_req word, square}
   int64_t* node_off;        // proofs + 1
   int64_t* leaf_off;        // proofs + 1
@@ -209,9 +192,6 @@ struct NsSqArgs {
 hipError_t launch_ns_sq_search(const NsSqArgs& a, hipStream_t s);
 // after the host has compared a.totals with the capacities
 hipError_t launch_ns_sq_scatter(const NsSqArgs& a, hipStream_t s);
-// launch_ns_leaf_nodes with record indexes counted from the start of the row region
-hipError_t launch_ns_sq_leaf_nodes(const uint8_t* store, const int64_t* rec_index, long n, uint8_t* out,
-                                   hipStream_t s);
 
 // Host-side level plan of one forest.  Leaves (level 0) are either packed tree
 // after tree (ragged: counts[t] leaves each) or uniform with (tstride,

@@ -12,8 +12,8 @@
 //                  90-B node (the proof's leaf hash).
 // Every record index is row * 2k + i with 0 <= row, i < 2k, or the row's root
 // record: nothing outside the row store is read.
-// The ns_sq_* kernels below do the same across the squares of a batch proof
-// store and lay the proofs out on the device.
+// The ns_sq_* kernels below run the same search (ns_find_row) across the
+// squares of a batch proof store and lay the proofs out on the device.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -38,6 +38,17 @@ __device__ __forceinline__ NsKey ns_key_load(const uint8_t* p) {
   return k;
 }
 
+// ns_find of query `query` (32 B, padded) on row tree `row` of the row store
+// `row_nodes`: the kind, and [*s, *e) unless it is kNsOutside
+__device__ __forceinline__ int ns_find_row(const uint8_t* row_nodes, long w, long row, const uint8_t* query,
+                                           uint32_t* s, uint32_t* e) {
+  // top level of the row store: lvl(log2 w) = 2 w^2 - 2 w (nmt_prove.hip)
+  const uint8_t* root = row_nodes + (2 * w * w - 2 * w + row) * kRecNmt;
+  const uint8_t* leaves = row_nodes + row * w * kRecNmt;
+  return ns_find(ns_key_load(query), ns_key_load(root), ns_key_load(root + 32), (uint32_t)w,
+                 [&](uint32_t i) { return ns_key_load(leaves + (long)i * kRecNmt); }, s, e);
+}
+
 }  // namespace
 
 __global__ __launch_bounds__(256) void ns_find_kernel(NsFindArgs a) {
@@ -45,26 +56,19 @@ __global__ __launch_bounds__(256) void ns_find_kernel(NsFindArgs a) {
   if (t >= a.n_q * a.w) return;
   const long q = t / a.w;
   const long row = t - q * a.w;
-  const long w = a.w, ww = w * w;
-  const NsKey nid = ns_key_load(a.queries + q * 32);
-  // top level of the row store: lvl(log2 w) = 2 w^2 - 2 w (nmt_prove.hip)
-  const uint8_t* root = a.row_nodes + (2 * ww - 2 * w + row) * kRecNmt;
-  const NsKey rmin = ns_key_load(root), rmax = ns_key_load(root + 32);
-  const uint8_t* leaves = a.row_nodes + row * w * kRecNmt;
   uint32_t s, e;
-  const int kind = ns_find(nid, rmin, rmax, (uint32_t)w,
-                           [&](uint32_t i) { return ns_key_load(leaves + (long)i * kRecNmt); }, &s, &e);
+  const int kind = ns_find_row(a.row_nodes, a.w, row, a.queries + q * 32, &s, &e);
   int32_t* o = a.ranges + t * kNsRangeWords;
   o[0] = kind;
   o[1] = (int32_t)s;
   o[2] = (int32_t)e;
 }
 
-__global__ __launch_bounds__(256) void ns_leaf_nodes_kernel(const uint8_t* row_nodes, const int64_t* rec_index, long n,
+__global__ __launch_bounds__(256) void ns_leaf_nodes_kernel(const uint8_t* base, const int64_t* rec_index, long n,
                                                             uint8_t* out) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const uint8_t* rec = row_nodes + rec_index[i] * kRecNmt;
+  const uint8_t* rec = base + rec_index[i] * kRecNmt;
   uint32_t mn[8], mx[8], dg[8];
   load_digest(rec, mn);
   load_digest(rec + 32, mx);
@@ -79,11 +83,10 @@ hipError_t launch_ns_find(const NsFindArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
-hipError_t launch_ns_leaf_nodes(const uint8_t* row_nodes, const int64_t* rec_index, long n, uint8_t* out,
-                                hipStream_t s) {
+hipError_t launch_ns_leaf_nodes(const uint8_t* base, const int64_t* rec_index, long n, uint8_t* out, hipStream_t s) {
   if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(ns_leaf_nodes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, row_nodes, rec_index,
-                     n, out);
+  hipLaunchKernelGGL(ns_leaf_nodes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, base, rec_index, n,
+                     out);
   return hipGetLastError();
 }
 
@@ -92,18 +95,20 @@ hipError_t launch_ns_leaf_nodes(const uint8_t* row_nodes, const int64_t* rec_ind
 // (dagpu_nmt_prove_namespace_squares_device; arithmetic and workspace in
 // ns_squares_layout.hpp).  One lane per (query, square, row), t = (query *
 // n_sq + square) * w + row, so ascending t is the order of the proofs.
-//   find        the search of ns_find_kernel on the row slice of the lane's
-//               square; the result is one packed word (0 = outside)
+//   find        ns_find_row on the row slice of the lane's square; the result
+//               is one packed word (0 = outside)
 //   block_sums  the four quantities of a block's 256 lanes, summed
 //   scan        exclusive scan of 4-word sums in place, 256 at a time: first
 //               every chunk of 256 block sums by a block of its own (its total
 //               goes to the chunk sums), then all chunk sums by one block that
 //               loops with a carry (its total is the batch's counts)
 //   scatter     each hit's position = block offset + chunk offset + its prefix
-//               inside the block; it writes the tables the prove_sq_* kernels
-//               read and the hit record for the host
+//               inside the block; it writes the tables the prove kernels read
+//               (two-word requests) and the hit record for the host
 //   per         one wave per (query, square): the hits among its w lanes
-//   leaf_nodes  ns_leaf_nodes_kernel with record indexes into the row region
+// The leaf hashes of absence proofs are ns_leaf_nodes_kernel's, with record
+// indexes counted from the start of the row region (square * records per
+// square + row * w + leaf).
 // Kernel boundaries are the only synchronisation between workgroups; positions
 // come from the scan alone, so the order is the lane order.  Every index is
 // below a count the host sized the tables by (lanes, blocks, chunks) or below
@@ -159,17 +164,11 @@ __device__ __forceinline__ NsSum ns_block_scan(const NsSum& x, int64_t (*sh)[kNs
 __global__ __launch_bounds__(256) void ns_sq_find_kernel(NsSqArgs a) {
   const long t = (long)blockIdx.x * 256 + threadIdx.x;
   if (t >= a.lanes) return;
-  const long w = a.w, ww = w * w;
+  const long w = a.w;
   const long pair = t / w, row = t - pair * w;
   const long q = pair / a.n_sq, sq = pair - q * a.n_sq;
-  const uint8_t* row_nodes = a.store + sq * a.row_bytes;
-  const NsKey nid = ns_key_load(a.queries + q * 32);
-  const uint8_t* root = row_nodes + (2 * ww - 2 * w + row) * kRecNmt;
-  const NsKey rmin = ns_key_load(root), rmax = ns_key_load(root + 32);
-  const uint8_t* leaves = row_nodes + row * w * kRecNmt;
   uint32_t s, e;
-  const int kind = ns_find(nid, rmin, rmax, (uint32_t)w,
-                           [&](uint32_t i) { return ns_key_load(leaves + (long)i * kRecNmt); }, &s, &e);
+  const int kind = ns_find_row(a.store + sq * a.row_bytes, w, row, a.queries + q * 32, &s, &e);
   a.words[t] = ns_sq_pack(kind, s, e);
 }
 
@@ -256,20 +255,6 @@ __global__ __launch_bounds__(256) void ns_sq_per_kernel(NsSqArgs a) {
   if ((threadIdx.x & 63) == 0) a.per[pair] = n;
 }
 
-// ns_leaf_nodes_kernel for a batch proof store: rec_index[i] counts 96-B records
-// from the start of the row region (square * records per square + row * w + leaf)
-__global__ __launch_bounds__(256) void ns_sq_leaf_nodes_kernel(const uint8_t* store, const int64_t* rec_index, long n,
-                                                               uint8_t* out) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const uint8_t* rec = store + rec_index[i] * kRecNmt;
-  uint32_t mn[8], mx[8], dg[8];
-  load_digest(rec, mn);
-  load_digest(rec + 32, mx);
-  load_digest(rec + 64, dg);
-  write_root(out + i * kNodeSize, mn, mx, dg);
-}
-
 hipError_t launch_ns_sq_search(const NsSqArgs& a, hipStream_t s) {
   if (a.lanes <= 0) return hipSuccess;
   hipLaunchKernelGGL(ns_sq_find_kernel, dim3((unsigned)a.blocks), dim3(256), 0, s, a);
@@ -283,14 +268,6 @@ hipError_t launch_ns_sq_search(const NsSqArgs& a, hipStream_t s) {
 hipError_t launch_ns_sq_scatter(const NsSqArgs& a, hipStream_t s) {
   if (a.lanes <= 0) return hipSuccess;
   hipLaunchKernelGGL(ns_sq_scatter_kernel, dim3((unsigned)a.blocks), dim3(256), 0, s, a);
-  return hipGetLastError();
-}
-
-hipError_t launch_ns_sq_leaf_nodes(const uint8_t* store, const int64_t* rec_index, long n, uint8_t* out,
-                                   hipStream_t s) {
-  if (n <= 0) return hipSuccess;
-  hipLaunchKernelGGL(ns_sq_leaf_nodes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, store, rec_index,
-                     n, out);
   return hipGetLastError();
 }
 

@@ -1,5 +1,5 @@
 // runtime.hpp -- internal host runtime shared by the C-ABI translation units
-// (dagpu.cpp, repair_host.cpp, trees.cpp, split.cpp): the context, device
+// (dagpu.cpp, repair_host.cpp, trees.cpp, prove_host.cpp, split.cpp): the context, device
 // buffers, error helpers and the per-kernel profiling bracket.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -23,7 +23,7 @@ mkdir -p "$OUT"
   python3 - "$(find "$TRACE" -name "*kernel_trace.csv" | head -1)" <<'PYEOF'
 import collections, csv, statistics, sys
 rows = [r for r in csv.DictReader(open(sys.argv[1]))
-        if "ns_sq_" in r["Kernel_Name"] or "prove_sq_" in r["Kernel_Name"]]
+        if any(f in r["Kernel_Name"] for f in ("ns_sq_", "ns_leaf_nodes", "prove_"))]
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 # the count call that sizes the capacities runs once before the four timed calls: skip its five kernels
 finds = [i for i, r in enumerate(rows) if "ns_sq_find" in r["Kernel_Name"]]
