@@ -73,6 +73,11 @@ EXPORTS = (
     "dagpu_square_plan_write_host",
     "dagpu_square_write_workspace_size",
     "dagpu_square_write_device",
+    "dagpu_square_plan_device_workspace_size",
+    "dagpu_square_plan_device_arena_size",
+    "dagpu_square_plan_device",
+    "dagpu_square_construct_device",
+    "dagpu_square_plan_emulate_host",
     "dagpu_blob_commitments_workspace_size",
     "dagpu_blob_commitments_device",
     "dagpu_square_plan_blobs",
@@ -134,6 +139,10 @@ EXPORTS = (
 COMMIT_MISMATCH = 1
 COMMIT_PUSH_ORDER = 2
 
+# dagpu_square_plan_device: status word = kind | index << 8
+PLAN_OK, PLAN_NO_SPACE_TX, PLAN_NO_SPACE_BLOB_TX, PLAN_TX_AFTER_BLOB_TX = 0, 1, 2, 3
+PLAN_LAYOUT, PLAN_TOO_MANY_BLOBS, PLAN_WIDTH, PLAN_ARENA = 4, 5, 6, 7
+PLAN_RECORD_BYTES = 32
 # dagpu_square_scan_device / dagpu_square_read_device (include/dagpu.h)
 SCAN_OK, SCAN_NAMESPACE, SCAN_INCONSISTENT, SCAN_LENGTH, SCAN_OVERFLOW = 0, 1, 2, 3, 4
 SCAN_SUMMARY_WORDS = 8
@@ -263,6 +272,15 @@ def lib() -> ctypes.CDLL:
         L.dagpu_square_write_workspace_size.argtypes = [sz, sz]
         L.dagpu_square_write_workspace_size.restype = sz
         L.dagpu_square_write_device.argtypes = [vp, ctypes.c_uint32, sz, vp, vp, vp, vp, sz, vp, sz, sz, vp, vp]
+        for f in (L.dagpu_square_plan_device_workspace_size, L.dagpu_square_plan_device_arena_size):
+            f.argtypes = [sz, sz, ctypes.c_uint32]
+            f.restype = sz
+        L.dagpu_square_plan_device.argtypes = [vp, sz, vp, vp, sz, vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp, sz,
+                                               vp, vp, vp, vp]
+        L.dagpu_square_construct_device.argtypes = [vp, ctypes.c_uint32, sz, vp, vp, sz, vp, vp, ctypes.c_uint32,
+                                                    ctypes.c_uint32, vp, sz, vp, vp, sz, sz, vp, vp, vp]
+        L.dagpu_square_plan_emulate_host.argtypes = [sz, vp, vp, sz, vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp, sz,
+                                                     vp, vp]
         L.dagpu_blob_commitments_workspace_size.argtypes = [ctypes.c_uint32, sz, sz]
         L.dagpu_blob_commitments_workspace_size.restype = sz
         L.dagpu_blob_commitments_device.argtypes = [vp, ctypes.c_uint32, sz, sz, vp, vp, sz, sz, ctypes.c_uint32, vp, vp,

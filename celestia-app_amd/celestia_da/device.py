@@ -572,6 +572,118 @@ def write_squares_device(k: int, plans, srcs, out: torch.Tensor, square_stride: 
     del host
 
 
+class PlannedSquares:
+    """What dagpu_square_plan_device / dagpu_square_construct_device left in
+    HBM for n blocks: the plan arena, one record and one status word per block
+    (square.plan_record_dtype, _abi.PLAN_*), and the packed txs they refer to.
+    Nothing is downloaded until it is asked for."""
+
+    def __init__(self, n, arena, records, status, src, src_lens, stream):
+        self.n, self.arena, self.records, self.status = n, arena, records, status
+        self.src, self.src_lens, self._stream = src, src_lens, stream
+        self._rec = self._plans = None
+
+    def status_host(self):
+        """The n status words: the one read a caller needs to go on."""
+        self._stream.synchronize()
+        return self.status[:self.n].cpu().numpy().view("<u4").copy()
+
+    def records_host(self):
+        from . import square as sq
+        if self._rec is None:
+            self._stream.synchronize()
+            self._rec = self.records.cpu().numpy().view(sq.plan_record_dtype())[:self.n].copy()
+        return self._rec
+
+    def plans_host(self):
+        """Each block's plan as a uint8 array (None for a rejected block): the
+        used part of the arena, downloaded once."""
+        import numpy as np
+        if self._plans is None:
+            rec = self.records_host()
+            used = int(max((int(r["plan_off"]) + int(r["plan_bytes"]) for r in rec), default=0))
+            arena = self.arena[:used].cpu().numpy() if used else np.zeros(0, np.uint8)
+            self._plans = [None if int(r["plan_bytes"]) == 0 else
+                           arena[int(r["plan_off"]):int(r["plan_off"]) + int(r["plan_bytes"])].copy() for r in rec]
+        return self._plans
+
+
+def plan_squares_device(blocks, max_square_size: int = 128, threshold: int = 64, device: int = 0,
+                        ctx: Optional[Context] = None, stream: Optional[torch.cuda.Stream] = None,
+                        k: Optional[int] = None, out: Optional[torch.Tensor] = None, square_stride: int = 0,
+                        row_pitch: int = 0, threads: int = 16) -> PlannedSquares:
+    """dagpu_square_plan_device over n blocks of raw txs (each a sequence of
+    bytes): one upload of the packed batch, then the planner's kernels; no
+    layout on the host.  With k and out (cuda uint8) it is
+    dagpu_square_construct_device: the squares of width k are written behind
+    the planner in the same enqueue, square i at out + i * square_stride, rows
+    row_pitch apart; a rejected block, or one of another width, leaves its
+    window untouched and says so in its status word.  Enqueued on `stream`."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    import numpy as np
+    c = ctx or default_context()
+    n = len(blocks)
+    dev = out.device if out is not None else torch.device("cuda", device)
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    # pack: the lengths, then every block's txs straight into the pinned staging
+    # buffer, blocks side by side on the pool (the copies release the GIL)
+    ntx = np.array([len(b) for b in blocks], np.uint32)
+    workers = max(1, min(16, int(threads), n))
+    pool = ThreadPoolExecutor(workers) if workers > 1 else None
+    each = pool.map if pool else map
+    per = list(each(lambda b: np.fromiter(map(len, b), np.uint64, len(b)), blocks))
+    lens = np.concatenate(per) if per else np.zeros(0, np.uint64)
+    offs = np.zeros(n + 1, np.uint64)
+    offs[1:] = np.cumsum([int(v.sum()) for v in per], dtype=np.uint64)
+    total = int(offs[n])
+    host = torch.empty((max(total, 1),), dtype=torch.uint8).pin_memory()
+    hv = host.numpy()
+
+    def fill(i):
+        if offs[i + 1] > offs[i]:
+            hv[int(offs[i]):int(offs[i + 1])] = np.frombuffer(b"".join(blocks[i]), np.uint8)
+    list(each(fill, range(n)))
+    if pool:
+        pool.shutdown()
+    cap = c._L.dagpu_square_plan_device_arena_size(n, int(lens.size), max_square_size)
+    with torch.cuda.stream(s):
+        d_src = host.to(dev, non_blocking=True)
+        arena = torch.empty((max(cap, 16),), dtype=torch.uint8, device=dev)
+        records = torch.empty((max(n, 1) * _abi.PLAN_RECORD_BYTES,), dtype=torch.uint8, device=dev)
+        status = torch.zeros((max(n, 4),), dtype=torch.int32, device=dev)
+        ws = torch.empty((max(c._L.dagpu_square_plan_device_workspace_size(n, int(lens.size), max_square_size), 16),),
+                         dtype=torch.uint8, device=dev)
+    common = (_abi.addr(d_src), _abi.addr(offs), total, _abi.addr(ntx),
+              _abi.addr(lens) if lens.size else None, max_square_size, threshold, _abi.addr(arena), cap,
+              _abi.addr(records))
+    if out is None:
+        rc = c._L.dagpu_square_plan_device(c.handle, n, *common, _abi.addr(status), _abi.addr(ws), _stream_handle(s))
+    else:
+        if out.dtype != torch.uint8 or not out.is_contiguous() or \
+                (n and out.numel() < (n - 1) * square_stride + (k - 1) * row_pitch + k * 512):
+            raise ValueError("out must be a contiguous cuda uint8 tensor holding n squares at the given strides")
+        rc = c._L.dagpu_square_construct_device(c.handle, k, n, *common, _abi.addr(out), square_stride, row_pitch,
+                                                _abi.addr(status), _abi.addr(ws), _stream_handle(s))
+    if rc != 0:
+        raise DAError(rc, c.last_error())
+    # the workspace is read by kernels still queued: torch's allocator reuses it
+    # only for work queued on the same stream behind them
+    del host
+    p = PlannedSquares(n, arena, records, status, d_src, [int(offs[i + 1] - offs[i]) for i in range(n)], s)
+    return p
+
+
+def construct_squares_device(k: int, blocks, out: torch.Tensor, square_stride: int, row_pitch: int,
+                             max_square_size: int = 128, threshold: int = 64, ctx: Optional[Context] = None,
+                             stream: Optional[torch.cuda.Stream] = None, threads: int = 16) -> PlannedSquares:
+    """dagpu_square_construct_device: plan n blocks of raw txs on the device
+    and write their squares of width k into `out`, in one enqueue (see
+    plan_squares_device)."""
+    return plan_squares_device(blocks, max_square_size, threshold, ctx=ctx, stream=stream, k=k, out=out,
+                               square_stride=square_stride, row_pitch=row_pitch, threads=threads)
+
+
 def blob_commitments_device(k: int, blobs, squares: torch.Tensor, square_stride: int, row_pitch: int,
                             expected=None, threshold: int = 64, ctx: Optional[Context] = None,
                             stream: Optional[torch.cuda.Stream] = None):
@@ -825,14 +937,24 @@ class DeviceSquares:
             self.ods.view(self.n, self.k, self.k * 512).copy_(src)
 
     def load_txs(self, blocks, stream: Optional[torch.cuda.Stream] = None, threads: int = 16,
-                 max_square_size: Optional[int] = None, threshold: Optional[int] = None) -> None:
+                 max_square_size: Optional[int] = None, threshold: Optional[int] = None, plan: str = "host") -> None:
         """n blocks of raw txs (each a sequence of bytes) -> their squares where
         extend() reads them, with no ODS on the host: every block is planned on
         the host (square.plan_native's dagpu_square_plan, on a pool of at most
         16 threads), txs and plans are uploaded and dagpu_square_write_device
         writes self.ods, or Q0 of the EDS at the EDS row pitch when in_place.
         Raises ShareError as square.construct_native does, and DAError when a
-        block's square width is not self.k (nothing is written then)."""
+        block's square width is not self.k (nothing is written then).
+
+        plan="device": no layout on the host.  One upload of the packed batch,
+        one dagpu_square_construct_device (classify, plan and write on the
+        GPU), one read of n status words.  A block the planner rejects is
+        planned again on the host (square.plan_native) to raise the same
+        ShareError / DAError with the same message, and as on the host route a
+        rejected block's error comes before any block's width error.  The one difference from
+        the host route: the accepted blocks' squares have been written when a
+        rejected block, or one of another width, raises.  The plans stay in HBM and are downloaded when
+        blob_table() / check_commitments() first ask for them."""
         from concurrent.futures import ThreadPoolExecutor
 
         from . import square as sq
@@ -844,17 +966,22 @@ class DeviceSquares:
         m = sq.SQUARE_SIZE_UPPER_BOUND if max_square_size is None else max_square_size
         t = sq.SUBTREE_ROOT_THRESHOLD if threshold is None else threshold
 
-        def plan(txs):
+        if plan == "device":
+            return self._load_txs_device(blocks, stream, m, t, threads)
+        if plan != "host":
+            raise ValueError("plan is 'host' or 'device'")
+
+        def plan_one(txs):
             buf, lens = sq._pack(txs)
             k, p = sq._plan_packed(buf, lens, len(txs), m, t)
             return k, p, buf[:int(lens.sum())]
 
         workers = max(1, min(16, int(threads), self.n))
         if workers == 1:
-            planned = [plan(b) for b in blocks]
+            planned = [plan_one(b) for b in blocks]
         else:
             with ThreadPoolExecutor(workers) as pool:
-                planned = list(pool.map(plan, blocks))
+                planned = list(pool.map(plan_one, blocks))
         for i, (k, _, _) in enumerate(planned):
             if k != self.k:
                 raise DAError(_abi.ERR_ARG, f"block {i} has square width {k}, these squares have width {self.k}")
@@ -865,6 +992,33 @@ class DeviceSquares:
                              pitch, ctx=self.ctx, stream=stream)
         self._plans = [p for _, p, _ in planned]
         self._src_lens = [int(b.size) for _, _, b in planned]
+
+    def _load_txs_device(self, blocks, stream, m: int, t: int, threads: int) -> None:
+        from . import square as sq
+        w = 2 * self.k
+        out, stride, pitch = ((self.eds, w * w * 512, w * 512) if self.in_place
+                              else (self.ods, self.k * self.k * 512, self.k * 512))
+        self._plans = self._src_lens = None
+        p = construct_squares_device(self.k, blocks, out.view(-1), stride, pitch, max_square_size=m, threshold=t,
+                                     ctx=self.ctx, stream=stream, threads=threads)
+        words = [sq.plan_status(v) + (int(v),) for v in p.status_host()]
+        # the host route plans every block before it looks at any width: a
+        # rejected block's error comes before any block's width error
+        for i, (kind, _, word) in enumerate(words):
+            if kind and kind != _abi.PLAN_WIDTH:
+                sq.plan_native(blocks[i], m, t)  # raises the host's error for this block
+                raise DAError(_abi.ERR_ARG, f"block {i}: the device planner's status {word} where the host "
+                                            f"planner accepts the block")
+        for i, (kind, index, _) in enumerate(words):
+            if kind == _abi.PLAN_WIDTH:
+                raise DAError(_abi.ERR_ARG, f"block {i} has square width {index}, these squares have width {self.k}")
+        self._plans = p  # downloaded by _host_plans when first asked for
+        self._src_lens = p.src_lens
+
+    def _host_plans(self):
+        if isinstance(self._plans, PlannedSquares):
+            self._plans = self._plans.plans_host()
+        return self._plans
 
     def blob_table(self):
         """Every blob of the batch load_txs wrote, block by block in plan order:
@@ -878,7 +1032,7 @@ class DeviceSquares:
         if self._plans is None:
             raise ValueError("no plans: blob_table follows load_txs")
         rec, key = [], []
-        for i, p in enumerate(self._plans):
+        for i, p in enumerate(self._host_plans()):
             t = sq.plan_blobs(p).astype(np.int64)
             rec.append(np.stack([np.full(len(t), i, np.int64), t[:, 0], t[:, 1]], axis=1))
             key.append(np.stack([np.full(len(t), i, np.int64), t[:, 2]], axis=1))

@@ -538,6 +538,83 @@ def construct_device(txs: Sequence[bytes], device: int = 0, ctx=None,
     return k, ods
 
 
+# ---- plan on the device (csrc/square_plan.hip dagpu_square_plan_device; the
+# same algorithm as host loops: dagpu_square_plan_emulate_host) ----------------
+
+def plan_record_dtype():
+    """One record of dagpu_square_plan_device per block."""
+    import numpy as np
+    return np.dtype([("plan_off", "<u8"), ("src_off", "<u8"), ("plan_bytes", "<u4"), ("k", "<u4"),
+                     ("status", "<u4"), ("nblob", "<u4")])
+
+
+def plan_status(word: int):
+    """(kind, index) of a planner status word (_abi.PLAN_*)."""
+    return int(word) & 0xFF, int(word) >> 8
+
+
+def pack_blocks(blocks, lead: int = 0):
+    """The planner's input for n blocks of txs: (src, src_offs, ntx, tx_lens):
+    every tx of every block back to back behind `lead` unused bytes (uint8),
+    the n + 1 block offsets (uint64), the tx count of each block (uint32) and
+    all tx lengths (uint64)."""
+    import numpy as np
+    flat = [bytes(t) for b in blocks for t in b]
+    src = np.frombuffer(bytes(lead) + b"".join(flat), np.uint8).copy()
+    lens = np.array([len(t) for t in flat], np.uint64)
+    ntx = np.array([len(b) for b in blocks], np.uint32)
+    offs = np.zeros(len(blocks) + 1, np.uint64)
+    at = lead
+    for i, b in enumerate(blocks):
+        offs[i] = at
+        at += sum(len(t) for t in b)
+    offs[len(blocks)] = at
+    return src, offs, ntx, lens
+
+
+def plan_of(arena, record):
+    """The plan a record names, cut from the (host) arena; None for a rejected block."""
+    if int(record["status"]) & 0xFF not in (0, 6) or int(record["plan_bytes"]) == 0:
+        return None
+    return arena[int(record["plan_off"]):int(record["plan_off"]) + int(record["plan_bytes"])]
+
+
+def plan_emulate(blocks, max_square_size: int = SQUARE_SIZE_UPPER_BOUND, threshold: int = SUBTREE_ROOT_THRESHOLD):
+    """dagpu_square_plan_emulate_host: the device planner's algorithm as host
+    loops over n blocks of txs.  Returns (arena, records, status): the plan
+    arena (uint8 array), one plan_record_dtype record and one status word per
+    block; plan_of(arena, records[i]) equals plan_native(blocks[i])[1] for an
+    accepted block, and status[i] is nonzero exactly when plan_native raises."""
+    import numpy as np
+
+    from . import _abi
+    L = _abi.lib()
+    n = len(blocks)
+    src, offs, ntx, lens = pack_blocks(blocks)
+    cap = L.dagpu_square_plan_device_arena_size(n, int(lens.size), max_square_size)
+    arena = np.zeros(max(cap, 16), np.uint8)
+    rec = np.zeros(max(n, 1), plan_record_dtype())
+    status = np.zeros(max(n, 4), np.uint32)
+    rc = L.dagpu_square_plan_emulate_host(n, _abi.addr(src) if src.size else None, _abi.addr(offs), src.size,
+                                          _abi.addr(ntx), _abi.addr(lens) if lens.size else None, max_square_size,
+                                          threshold, _abi.addr(arena), cap, _abi.addr(rec), _abi.addr(status))
+    if rc != 0:
+        raise ValueError(f"dagpu_square_plan_emulate_host: status {rc}: {L.dagpu_last_error(None).decode()}")
+    return arena, rec[:n], status[:n]
+
+
+def plan_device(blocks, max_square_size: int = SQUARE_SIZE_UPPER_BOUND, threshold: int = SUBTREE_ROOT_THRESHOLD,
+                device: int = 0, ctx=None, stream=None):
+    """dagpu_square_plan_device over n blocks of txs: one upload of the packed
+    txs, the planner's kernels, no host layout.  Returns (arena, records,
+    status): the plan arena as a cuda uint8 tensor, and the records and status
+    words downloaded (numpy, as plan_emulate returns them)."""
+    from .device import plan_squares_device
+    p = plan_squares_device(blocks, max_square_size=max_square_size, threshold=threshold, device=device, ctx=ctx,
+                            stream=stream)
+    return p.arena, p.records_host(), p.status_host()
+
+
 def tx_share_range(txs: Sequence[bytes], tx_index: int, app_version: int = LATEST_VERSION) -> Range:
     return Builder(square_size_upper_bound(app_version), app_version, *txs).find_tx_share_range(tx_index)
 

@@ -29,19 +29,21 @@
 #include <string.h>
 
 #include <algorithm>
-#include <cmath>
 #include <string>
 #include <vector>
 
 #include "../../include/dagpu.h"
 #include "runtime.hpp"
+#include "square_plan.hpp"
 #include "square_write.hpp"
 
 namespace {
 
+// the parse and layout arithmetic: square_plan.hpp, shared with the device planner
+using namespace dagpu;
+
 constexpr size_t kShare = 512, kNs = 29, kNsId = 28;
 constexpr size_t kFirstCompact = 474, kContCompact = 478;  // content bytes
-constexpr size_t kFirstSparse = 478, kContSparse = 482;
 
 struct SquareError {
   std::string msg;
@@ -69,32 +71,12 @@ const Ns kTailPaddingNs = secondary_reserved(0xFE);
 
 // namespace.From: version 0 or 255; a version-0 ID starts with 18 zero bytes
 void validate_namespace(const uint8_t* ns) {
-  const uint8_t v = ns[0];
-  if (v != 0 && v != 255) throw SquareError{"unsupported namespace version " + std::to_string(v)};
-  if (v == 0)
-    for (int i = 1; i <= 18; i++)
-      if (ns[i])
-        throw SquareError{"unsupported namespace id with version 0. ID must start with 18 leading zeros"};
+  const int fault = namespace_fault(ns);
+  if (fault == 1) throw SquareError{"unsupported namespace version " + std::to_string(ns[0])};
+  if (fault == 2)
+    throw SquareError{"unsupported namespace id with version 0. ID must start with 18 leading zeros"};
 }
 
-// ---- varints / proto wire format ---------------------------------------------
-size_t uvarint_len(uint64_t v) {
-  size_t n = 1;
-  while (v >= 0x80) {
-    v >>= 7;
-    n++;
-  }
-  return n;
-}
-size_t put_uvarint(uint8_t* out, uint64_t v) {
-  size_t n = 0;
-  while (v >= 0x80) {
-    out[n++] = (uint8_t)(v | 0x80);
-    v >>= 7;
-  }
-  out[n++] = (uint8_t)v;
-  return n;
-}
 void append_uvarint(std::vector<uint8_t>& o, uint64_t v) {
   uint8_t b[10];
   o.insert(o.end(), b, b + put_uvarint(b, v));
@@ -105,101 +87,32 @@ struct Span {
   size_t n = 0;
 };
 
-bool read_varint(const uint8_t* b, size_t n, size_t& i, uint64_t& v) {
-  v = 0;
-  for (unsigned s = 0;; s += 7) {
-    if (i >= n || s >= 64) return false;  // unexpected EOF / integer overflow
-    const uint8_t c = b[i++];
-    v |= (uint64_t)(c & 0x7F) << s;
-    if (c < 0x80) return true;
-  }
-}
-
-// gogoproto-style field walk: calls f(num, wire type, varint, bytes); false on
-// a malformed buffer or when f rejects a field (wrong wire type).
-template <class F>
-bool walk_fields(Span buf, F&& f) {
-  size_t i = 0;
-  while (i < buf.n) {
-    uint64_t key, v = 0;
-    if (!read_varint(buf.p, buf.n, i, key)) return false;
-    const uint64_t num = key >> 3;
-    const int wt = (int)(key & 7);
-    if (num == 0) return false;
-    Span bytes;
-    switch (wt) {
-      case 0:
-        if (!read_varint(buf.p, buf.n, i, v)) return false;
-        break;
-      case 1:
-        if (i + 8 > buf.n) return false;
-        i += 8;
-        break;
-      case 2: {
-        uint64_t len;
-        if (!read_varint(buf.p, buf.n, i, len) || len > buf.n - i) return false;
-        bytes = {buf.p + i, (size_t)len};
-        i += (size_t)len;
-        break;
-      }
-      case 5:
-        if (i + 4 > buf.n) return false;
-        i += 4;
-        break;
-      default:
-        return false;
-    }
-    if (!f(num, wt, v, bytes)) return false;
-  }
-  return true;
-}
-
 struct BlobRef {
   Span ns_id, data;
   uint32_t share_version = 0, ns_version = 0;
 };
 
-// blob.UnmarshalBlobTx: is a blob tx iff it decodes, type_id == "BLOB", it
-// carries blobs and every namespace ID is 28 bytes
-bool unmarshal_blob_tx(Span buf, Span& inner, std::vector<BlobRef>& blobs) {
+// blob.UnmarshalBlobTx (sp_unmarshal_blob_tx): is a blob tx iff it decodes,
+// type_id == "BLOB", it carries blobs and every namespace ID is 28 bytes
+bool unmarshal_blob_tx(Span buf, Span& inner, std::vector<BlobRef>& blobs, std::vector<SpBlobFields>& f) {
   blobs.clear();
   inner = {};
-  Span type_id;
-  const bool ok = walk_fields(buf, [&](uint64_t num, int wt, uint64_t, Span b) {
-    if (num == 1) {
-      if (wt != 2) return false;
-      inner = b;
-    } else if (num == 2) {
-      if (wt != 2) return false;
-      BlobRef r;
-      const bool ok2 = walk_fields(b, [&](uint64_t n2, int w2, uint64_t v2, Span b2) {
-        if (n2 == 1) {
-          if (w2 != 2) return false;
-          r.ns_id = b2;
-        } else if (n2 == 2) {
-          if (w2 != 2) return false;
-          r.data = b2;
-        } else if (n2 == 3) {
-          if (w2 != 0) return false;
-          r.share_version = (uint32_t)v2;
-        } else if (n2 == 4) {
-          if (w2 != 0) return false;
-          r.ns_version = (uint32_t)v2;
-        }
-        return true;
-      });
-      if (!ok2) return false;
-      blobs.push_back(r);
-    } else if (num == 3) {
-      if (wt != 2) return false;
-      type_id = b;
-    }
-    return true;
-  });
-  if (!ok) return false;
-  if (type_id.n != 4 || memcmp(type_id.p, "BLOB", 4) != 0 || blobs.empty()) return false;
-  for (const auto& b : blobs)
-    if (b.ns_id.n != kNsId) return false;
+  // one pass in fill mode into the caller's scratch, which only grows: a blob
+  // of a blob tx carries a 28-byte namespace ID, so it has 32 bytes or more
+  if (f.size() < buf.n / 32 + 1) f.resize(buf.n / 32 + 1);
+  const SpTxInfo info =
+      sp_unmarshal_blob_tx(buf.p, (uint32_t)buf.n, 0, f.data(), (uint32_t)f.size(), sizeof(SpBlobFields));
+  if (!info.is_blob_tx) return false;
+  inner = {buf.p + info.inner_off, info.inner_len};
+  for (uint32_t j = 0; j < info.nblob; j++) {
+    const SpBlobFields& b = f[j];
+    BlobRef r;
+    r.ns_id = {buf.p + b.ns_off, b.ns_len};
+    r.data = {buf.p + b.data_off, b.data_len};
+    r.share_version = b.share_version;
+    r.ns_version = b.ns_version;
+    blobs.push_back(r);
+  }
   return true;
 }
 
@@ -221,53 +134,6 @@ void marshal_index_wrapper(Span tx, const std::vector<uint32_t>& idx, std::vecto
   o.push_back(0x1a);
   o.push_back(4);
   o.insert(o.end(), {'I', 'N', 'D', 'X'});
-}
-size_t index_wrapper_size(size_t tx_len, size_t n_idx, uint32_t each) {
-  size_t s = 6;  // type_id field
-  if (tx_len) s += 1 + uvarint_len(tx_len) + tx_len;
-  if (n_idx) {
-    const size_t packed = n_idx * uvarint_len(each);
-    s += 1 + uvarint_len(packed) + packed;
-  }
-  return s;
-}
-
-size_t index_wrapper_size(size_t tx_len, const std::vector<uint32_t>& idx) {
-  size_t s = 6;  // type_id field
-  if (tx_len) s += 1 + uvarint_len(tx_len) + tx_len;
-  if (!idx.empty()) {
-    size_t packed = 0;
-    for (uint32_t x : idx) packed += uvarint_len(x);
-    s += 1 + uvarint_len(packed) + packed;
-  }
-  return s;
-}
-
-// ---- shares ---------------------------------------------------------------------
-uint64_t round_up_pow2(uint64_t v) {
-  uint64_t r = 1;
-  while (r < v) r <<= 1;
-  return r;
-}
-uint64_t blob_min_square_size(uint64_t share_count) {
-  return round_up_pow2((uint64_t)std::ceil(std::sqrt((double)share_count)));
-}
-uint64_t subtree_width_u(uint64_t share_count, uint64_t threshold) {
-  uint64_t s = share_count / threshold + (share_count % threshold ? 1 : 0);
-  s = round_up_pow2(s);
-  const uint64_t m = blob_min_square_size(share_count);
-  return s < m ? s : m;
-}
-uint64_t sparse_shares_needed(uint64_t len) {
-  if (len == 0) return 0;
-  if (len < kFirstSparse) return 1;
-  return 1 + (len - kFirstSparse + kContSparse - 1) / kContSparse;
-}
-// shares.CompactSharesNeeded: compact shares a unit stream of len bytes fills
-uint64_t compact_shares_needed(uint64_t len) {
-  if (len == 0) return 0;
-  if (len <= kFirstCompact) return 1;
-  return 1 + (len - kFirstCompact + kContCompact - 1) / kContCompact;
 }
 void put_be32(uint8_t* p, uint32_t v) {
   p[0] = (uint8_t)(v >> 24);
@@ -477,7 +343,7 @@ class SquareBuilder {
     for (size_t i = 0; i < blobs_.size(); i++) {
       Element& e = blobs_[i];
       const uint64_t wdt = subtree_width_u(e.num_shares, threshold_);
-      cursor = cursor % wdt == 0 ? cursor : (cursor / wdt + 1) * wdt;  // NextShareIndex
+      cursor = next_share_index(cursor, wdt);
       if (i == 0) non_reserved_start = cursor;
       const uint64_t padding = cursor - end_of_last;
       if (padding > e.max_padding)
@@ -498,7 +364,7 @@ class SquareBuilder {
       end_of_last = cursor;
     }
     for (const PfbRec& p : pfbs_) {
-      const size_t iw = index_wrapper_size(p.tx.n, p.share_indexes);
+      const size_t iw = index_wrapper_size(p.tx.n, p.share_indexes.data(), p.share_indexes.size());
       l.pfb_len += uvarint_len(iw) + iw;
     }
     const uint64_t pfb_count = compact_shares_needed(l.pfb_len);
@@ -602,7 +468,7 @@ class SquareBuilder {
       std::vector<uint8_t> tail;
       for (const PfbRec& p : pfbs_) {
         seq[1].unit.push_back(seq[1].pos);
-        size_t n = put_uvarint(tmp, index_wrapper_size(p.tx.n, p.share_indexes));
+        size_t n = put_uvarint(tmp, index_wrapper_size(p.tx.n, p.share_indexes.data(), p.share_indexes.size()));
         if (p.tx.n) {  // marshal_index_wrapper's bytes around the inner tx
           tmp[n++] = 0x0a;
           n += put_uvarint(tmp + n, p.tx.n);
@@ -701,6 +567,8 @@ std::vector<Span> split_txs(const uint8_t* txs, const uint64_t* lens, size_t ntx
   std::vector<Span> v(ntx);
   size_t off = 0;
   for (size_t i = 0; i < ntx; i++) {
+    // the parser of square_plan.hpp walks a tx with 32-bit offsets
+    if (lens[i] > 0xFFFFFFFFull) throw SquareError{"tx at index " + std::to_string(i) + " has 4 GiB or more"};
     v[i] = {txs + off, (size_t)lens[i]};
     off += (size_t)lens[i];
   }
@@ -711,13 +579,14 @@ std::vector<Span> split_txs(const uint8_t* txs, const uint64_t* lens, size_t ntx
 // square.Build (what does not fit is skipped, kept[i] = 0)
 void append_all(SquareBuilder& b, const std::vector<Span>& v, bool build, uint8_t* kept) {
   std::vector<BlobRef> blobs;
+  std::vector<SpBlobFields> scratch;
   bool seen_blob = false;
   for (size_t i = 0; i < v.size(); i++) {
     Span inner;
     if (build) {
-      const bool ok = unmarshal_blob_tx(v[i], inner, blobs) ? b.append_blob_tx(inner, blobs) : b.append_tx(v[i]);
+      const bool ok = unmarshal_blob_tx(v[i], inner, blobs, scratch) ? b.append_blob_tx(inner, blobs) : b.append_tx(v[i]);
       if (kept) kept[i] = ok ? 1 : 0;
-    } else if (unmarshal_blob_tx(v[i], inner, blobs)) {
+    } else if (unmarshal_blob_tx(v[i], inner, blobs, scratch)) {
       seen_blob = true;
       if (!b.append_blob_tx(inner, blobs))
         throw SquareError{"not enough space to append blob tx at index " + std::to_string(i)};

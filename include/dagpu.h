@@ -840,7 +840,11 @@ int dagpu_nmt_prove_namespace_squares_device(dagpu_ctx* ctx, uint32_t k, size_t 
  * ("not enough space to append tx at index 3", ...).  max_square_size =
  * SquareSizeUpperBound (128) and subtree_root_threshold = 64 for app v1.
  * The ODS goes straight into dagpu_extend_shares / the device batch API.
- * ctx may be NULL (then no message is kept).  No device work. */
+ * ctx may be NULL (then no message is kept).  No device work.
+ * A single tx of 4 GiB or more is refused (DAGPU_ERR_SQUARE, "tx at index i
+ * has 4 GiB or more"), here and in dagpu_square_build / dagpu_square_plan: the
+ * BlobTx parser shared with the device planner (csrc/square_plan.hpp) walks a
+ * tx with 32-bit offsets. */
 int dagpu_square_construct(dagpu_ctx* ctx, const uint8_t* txs, const uint64_t* tx_lens, size_t ntx,
                            uint32_t max_square_size, uint32_t subtree_root_threshold, uint8_t* ods_out,
                            size_t ods_cap, uint32_t* square_size);
@@ -874,7 +878,10 @@ int dagpu_square_build(dagpu_ctx* ctx, const uint8_t* txs, const uint64_t* tx_le
  * size and src_bytes of txs, the runs covering shares 0 .. k*k-1 once and in
  * order, and the order of the tables the writer searches; DAGPU_ERR_ARG on any
  * violation (message: dagpu_last_error(NULL)).  The writers trust a plan only
- * after it: both run it first.
+ * after it: both run it first.  The one exception is
+ * dagpu_square_construct_device (below), whose writer takes plans the device
+ * planner has just made in device memory and trusts them on the planner's
+ * own bounds.
  *
  * dagpu_square_plan_write_host: the square of a plan and its txs, row r at
  * ods_out + r * row_pitch (row_pitch >= k*512; bytes between rows untouched). */
@@ -906,6 +913,90 @@ int dagpu_square_write_device(dagpu_ctx* ctx, uint32_t k, size_t n, const uint8_
                               const size_t* plan_bytes, const uint8_t* d_src, const size_t* src_offs,
                               size_t src_bytes, uint8_t* d_ods, size_t square_stride, size_t row_pitch,
                               void* d_workspace, void* stream);
+
+/* ---- Square plans made on the device: raw txs to plans with no host pass ---
+ * dagpu_square_plan (kept == NULL, square.Construct) for n blocks at once, on
+ * the device: the packed txs of the blocks are in HBM (d_src, src_offs[n + 1]
+ * HOST offsets as in dagpu_square_write_device, each block below 2 GiB), ntx[n]
+ * (HOST) is each block's tx count and tx_lens (HOST) the lengths of all blocks'
+ * txs back to back; every block's lengths must add up to its src_offs span.
+ * The library uploads the lengths in one copy, then two kernels run on
+ * `stream` (csrc/square_plan.hip; arithmetic csrc/square_plan.hpp, shared with
+ * dagpu_square_plan): one lane per tx classifies it (blob.UnmarshalBlobTx),
+ * one workgroup per block replays Construct's append loop as a scan, sorts
+ * the blobs, walks NextShareIndex, sizes the PFB stream and emits the plan.
+ * max_square_size: a power of two <= 128, else DAGPU_ERR_UNSUPPORTED;
+ * square.Build (kept != NULL) is not offered.  Outputs, all DEVICE, 16-B
+ * aligned:
+ *   d_plans    the plan arena, plans_cap bytes.  Block i's plan is byte for
+ *              byte what dagpu_square_plan returns for it, at a 16-B aligned
+ *              offset the device chooses (one atomic add per block: the order
+ *              of the plans in the arena is not fixed).
+ *   d_records  n records of 32 bytes { uint64 plan_off, uint64 src_off,
+ *              uint32 plan_bytes, k, status, nblob }: where the plan lies, the
+ *              square width found, the status below.  plan_bytes = 0 for a
+ *              rejected block: it gets no plan.
+ *   d_status   n uint32: 0, or kind | index << 8, nonzero exactly for the
+ *              blocks dagpu_square_plan rejects, the first error in its order:
+ *                DAGPU_PLAN_NO_SPACE_TX / _NO_SPACE_BLOB_TX / _TX_AFTER_BLOB_TX
+ *                    with the tx index of the reference's message
+ *                DAGPU_PLAN_LAYOUT    any error of Export / WriteSquare, with
+ *                    the index of the blob in namespace order where there is one
+ *                DAGPU_PLAN_TOO_MANY_BLOBS  more than max_square_size^2 blobs
+ *                    (an empty blob fails Export, any other costs a share)
+ *                DAGPU_PLAN_ARENA     plans_cap is below the bound
+ * The message of a rejected block is dagpu_square_plan's on that block.
+ * Bounds: a block of t txs has a plan of at most 216 + 41 t + 51 m^2 bytes
+ * (m = max_square_size: 2 segments and 1 unit per tx, 48 B per blob, 5 B of
+ * delimiter per tx, 21 B of IndexWrapper head and tail per PFB, 3 B per share
+ * index); dagpu_square_plan_device_arena_size(n, ntx_total, m) is the sum over
+ * the blocks.  dagpu_square_plan_device_workspace_size(n, ntx_total, m) =
+ * 16 + 32 n + 64 ntx_total + n * (32 KiB + 64 m^2) bytes: 64 B per tx of
+ * tables, 64 B per possible blob, the sorted order.  For 256 full blocks
+ * (4,000 txs each, m = 128) that is 0.34 GB of workspace and 0.26 GB of arena;
+ * the plans themselves take 0.2 MB per block.  d_workspace (16-B aligned) must
+ * stay valid until the kernels have run; with NULL the library allocates it
+ * and waits.  Checked before anything is enqueued: null pointers, alignment,
+ * ascending src_offs, the tx_lens sums, the 2 GiB and 2^24 txs per block.
+ * Every kernel read of d_src stays inside the tx it parses: a length field
+ * that points past its tx rejects the tx as a blob tx, it is not followed.
+ *
+ * dagpu_square_construct_device: the same, then the squares of width k written
+ * as dagpu_square_write_device writes them (d_ods, square_stride, row_pitch),
+ * from the device's records with no host synchronisation between.  A block
+ * with a nonzero status, or whose width is not k (its status becomes
+ * DAGPU_PLAN_WIDTH | found width << 8), is skipped: not a byte of its square's
+ * window is touched.  The writers above trust a plan only after
+ * dagpu_square_plan_check; this one trusts the plans the planner has just made
+ * in device memory the caller has not touched, on the bounds above.
+ *
+ * dagpu_square_plan_emulate_host: the same arguments and outputs in HOST
+ * memory, the kernels' algorithm run as host loops (256 lanes per phase, the
+ * same scan chunks and sorting network); plans lie in block order.  For tests
+ * and for planning without a device.  No context. */
+#define DAGPU_PLAN_NO_SPACE_TX 1
+#define DAGPU_PLAN_NO_SPACE_BLOB_TX 2
+#define DAGPU_PLAN_TX_AFTER_BLOB_TX 3
+#define DAGPU_PLAN_LAYOUT 4
+#define DAGPU_PLAN_TOO_MANY_BLOBS 5
+#define DAGPU_PLAN_WIDTH 6
+#define DAGPU_PLAN_ARENA 7
+#define DAGPU_PLAN_RECORD_BYTES 32
+size_t dagpu_square_plan_device_workspace_size(size_t n, size_t ntx_total, uint32_t max_square_size);
+size_t dagpu_square_plan_device_arena_size(size_t n, size_t ntx_total, uint32_t max_square_size);
+int dagpu_square_plan_device(dagpu_ctx* ctx, size_t n, const uint8_t* d_src, const size_t* src_offs, size_t src_bytes,
+                             const uint32_t* ntx, const uint64_t* tx_lens, uint32_t max_square_size,
+                             uint32_t subtree_root_threshold, uint8_t* d_plans, size_t plans_cap, void* d_records,
+                             uint32_t* d_status, void* d_workspace, void* stream);
+int dagpu_square_construct_device(dagpu_ctx* ctx, uint32_t k, size_t n, const uint8_t* d_src, const size_t* src_offs,
+                                  size_t src_bytes, const uint32_t* ntx, const uint64_t* tx_lens,
+                                  uint32_t max_square_size, uint32_t subtree_root_threshold, uint8_t* d_plans,
+                                  size_t plans_cap, void* d_records, uint8_t* d_ods, size_t square_stride,
+                                  size_t row_pitch, uint32_t* d_status, void* d_workspace, void* stream);
+int dagpu_square_plan_emulate_host(size_t n, const uint8_t* src, const size_t* src_offs, size_t src_bytes,
+                                   const uint32_t* ntx, const uint64_t* tx_lens, uint32_t max_square_size,
+                                   uint32_t subtree_root_threshold, uint8_t* plans, size_t plans_cap, void* records,
+                                   uint32_t* status);
 
 /* ---- Share commitments from squares resident in HBM ----------------------
  * ProcessProposal recomputes every blob's share commitment and compares it
