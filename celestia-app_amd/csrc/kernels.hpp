@@ -335,7 +335,9 @@ struct SquareArgs {
 // Leaf digests (and Q0 namespaces) of rows [row0, row0 + nrows) of every
 // square (nrows < 0: to the last row).  zero_status (row0 == 0 only): the
 // launch also clears status[0 .. nsq), before the level-1 kernel queued behind
-// it ORs the push-order bit in.
+// it ORs the push-order bit in.  The leaf and tree-level launchers return
+// hipErrorInvalidValue for a k that is no power of two (nmt_coords.hpp: their
+// index maps are shifts and masks) or wider than kMaxK.
 hipError_t launch_nmt_leaves(const SquareArgs& a, hipStream_t s, int row0 = 0, int nrows = -1,
                              bool zero_status = false);
 // workspace layout for SquareArgs (digests | ns_table | rec_a | rec_b)

@@ -31,11 +31,14 @@
 #include <stdlib.h>
 
 #include "kernels.hpp"
+#include "nmt_coords.hpp"
 #include "nmt_node.hpp"
 #include "pipe_carve.hpp"
 #include "sha256.hpp"
 
 namespace dagpu {
+
+static_assert(kNmtMaxK == kMaxK, "the 32-bit lane offsets of nmt_coords.hpp are bounded for k <= kMaxK");
 
 // ---------------------------------------------------------------------------
 // Kernel 1: leaf digests.  digest(r,c) = SHA256(0x00 | P | share), where
@@ -55,28 +58,33 @@ constexpr int kLeafWave = 256;
 // batch hashes rows 0..k-1 ([Q0|Q1], final after the row pass) while the
 // column pass still runs.  With zero_status the lane of cell (0, 0) clears its
 // square's status word, which the level-1 kernel behind it on the stream ORs into.
-__global__ __launch_bounds__(kLeafWave) void nmt_leaf_kernel(SquareArgs a, int row0, int nrows, int zero_status) {
-  const int k = a.k;
-  const long w = 2L * k;
-  const long cells = w * w;
-  const long span = nrows * w;  // cells of one square in this launch
-  const long total = span * a.nsq;
-  const long gid = (long)blockIdx.x * kLeafWave + threadIdx.x;
-  if (gid >= total) return;
-  const long sq = gid / span;
-  const long cell = row0 * w + (gid - sq * span);
-  const long r = cell / w, c = cell - (cell / w) * w;
-  const bool q0 = (r < k) && (c < k);
-  if (zero_status && cell == 0) a.status[sq] = 0;
-  const uint4* src = (const uint4*)(a.eds + sq * a.eds_sq_stride + cell * kShareSize);
+// kWide (nmt_coords.hpp): the square and the workgroup's first cell are scalars
+// from blockIdx.x and a lane adds threadIdx.x; otherwise squares share a workgroup.
+// Scheduled for 4 waves per SIMD (120 VGPRs): the nine compressions then
+// interleave more independent work per wave; held to 6 waves (75 VGPRs) the
+// kernel alone ran the same and the pipelined k = 128 step 0.05 ms slower
+// (profiles/nmt_coords_ab.log).
+template <bool kWide>
+__global__ __launch_bounds__(kLeafWave) __attribute__((amdgpu_waves_per_eu(4, 4))) void nmt_leaf_kernel(
+    SquareArgs a, LeafMap m, int zero_status) {
+  const LeafCell lc = leaf_cell<kWide>(m, blockIdx.x, threadIdx.x);
+  if (!lc.valid) return;
+  const int lk = m.lw - 1;
+  const uint32_t r = leaf_row(m, lc), c = leaf_col(m, lc);
+  const bool q0 = ((r | c) >> lk) == 0;  // r < k && c < k
+  if (zero_status && lc.cell_u + lc.lane == 0) a.status[lc.sq] = 0;
+  const uint8_t* src_u = a.eds + lc.sq * a.eds_sq_stride + (long)lc.cell_u * kShareSize;
+  const uint4* src = (const uint4*)(src_u + lc.lane * (uint32_t)kShareSize);
   uint32_t st[8], ns[8];
   share_leaf_sha256(src, q0, st, ns);
   if (q0) {  // dense Q0 namespace table (29 B, zero padded to 32)
-    uint4* nsp = (uint4*)(a.ns_table + (sq * k * k + r * k + c) * 32);
+    uint8_t* ns_u = a.ns_table + (lc.sq << (2 * lk + 5));
+    uint4* nsp = (uint4*)(ns_u + (((r << lk) + c) << 5));
     nsp[0] = make_uint4(ns[0], ns[1], ns[2], ns[3]);
     nsp[1] = make_uint4(ns[4], ns[5], ns[6], ns[7]);
   }
-  uint4* out = (uint4*)(a.digests + (sq * cells + cell) * kDigest);
+  uint8_t* out_u = a.digests + ((lc.sq << (2 * m.lw)) + lc.cell_u) * kDigest;
+  uint4* out = (uint4*)(out_u + lc.lane * (uint32_t)kDigest);
   out[0] = make_uint4(bswap32(st[0]), bswap32(st[1]), bswap32(st[2]), bswap32(st[3]));
   out[1] = make_uint4(bswap32(st[4]), bswap32(st[5]), bswap32(st[6]), bswap32(st[7]));
 }
@@ -109,7 +117,7 @@ __device__ __forceinline__ void ns_by_ref(const uint8_t* ns_sq, uint32_t ref, ui
     for (int i = 0; i < 7; i++) ns[i] = 0xFFFFFFFFu;
     ns[7] = 0xFFu;
   } else {
-    const uint4* p = (const uint4*)(ns_sq + (long)ref * 32);
+    const uint4* p = (const uint4*)(ns_sq + (ref << 5));  // ref < k^2 <= 2^26 (kNmtMaxK)
     const uint4 v0 = p[0], v1 = p[1];
     ns[0] = v0.x; ns[1] = v0.y; ns[2] = v0.z; ns[3] = v0.w;
     ns[4] = v1.x; ns[5] = v1.y; ns[6] = v1.z; ns[7] = v1.w;
@@ -118,50 +126,36 @@ __device__ __forceinline__ void ns_by_ref(const uint8_t* ns_sq, uint32_t ref, ui
 
 // Level 1: pairs of leaves.  Leaf node = ns | ns | digest; a Q0 leaf whose
 // namespace equals the parity namespace gets kParityRef (same bytes).
-__device__ __forceinline__ void level_coords(long gid, int w, int per, long& sq, int& axis, int& idx, int& p) {
-  const long blk = 2L * w * per;  // records of one square at this level
-  sq = gid / blk;
-  const long g = gid - sq * blk;
-  axis = g >= (long)w * per;
-  const long g2 = g - (axis ? (long)w * per : 0);
-  if (axis == 0) { idx = (int)(g2 / per); p = (int)(g2 - (long)idx * per); }
-  else { p = (int)(g2 / w); idx = (int)(g2 - (long)p * w); }
-}
-
-// record index of node (axis, idx, p) of square sq at a level with `per` nodes per tree
-__device__ __forceinline__ long level_rec(long sq, int w, int per, int axis, int idx, int p) {
-  const long base = sq * 2L * w * per;
-  return axis == 0 ? base + (long)idx * per + p : base + (long)w * per + (long)p * w + idx;
-}
-
-__global__ __launch_bounds__(256) void nmt_level1_kernel(SquareArgs a, uint8_t* out_rec, int final_level) {
-  const int k = a.k;
-  const int w = 2 * k;
-  const int half = w / 2;
-  const long gid = (long)blockIdx.x * 256 + threadIdx.x;
-  const long total = a.nsq * 2L * w * half;
-  if (gid >= total) return;
-  long sq;
-  int axis, idx, p;
-  level_coords(gid, w, half, sq, axis, idx, p);
-  const uint8_t* dig = a.digests + sq * (long)w * w * kDigest;
-  const uint8_t* ns_sq = a.ns_table + sq * (long)k * k * 32;
-  const int j0 = 2 * p, j1 = 2 * p + 1;
-  const long cell0 = axis == 0 ? (long)idx * w + j0 : (long)j0 * w + idx;
-  const long cell1 = axis == 0 ? (long)idx * w + j1 : (long)j1 * w + idx;
+// kWide (nmt_coords.hpp, both level kernels): square, axis and the workgroup's
+// first node are scalars from blockIdx.x and a lane adds threadIdx.x in 32 bits;
+// otherwise (fewer than 256 nodes per square and axis) squares share a workgroup.
+template <bool kWide>
+__global__ __launch_bounds__(256) void nmt_level1_kernel(SquareArgs a, LevelMap m, uint8_t* out_rec,
+                                                         int final_level) {
+  const LevelNode n = level_node<kWide>(m, blockIdx.x, threadIdx.x);
+  if (!n.valid) return;
+  const int lk = m.lw - 1;
+  const uint32_t k = 1u << lk;
+  const long sq = n.sq;
+  const uint32_t axis = n.axis, idx = level_tree(m, n), p = level_pos(m, n);
+  const uint8_t* dig_u = a.digests + level_child_u(m, n, true) * kDigest;
+  const uint32_t c0 = level_child_l(m, n) * (uint32_t)kDigest;
+  const uint32_t c1 = c0 + level_child_step(m, n) * (uint32_t)kDigest;
+  const uint8_t* ns_sq = a.ns_table + (sq << (2 * lk + 5));
+  const uint32_t j0 = 2 * p, j1 = 2 * p + 1;
   const bool q00 = (idx < k) && (j0 < k), q01 = (idx < k) && (j1 < k);
   // Q0 ref = r*k + c
-  const uint32_t ref0 = q00 ? (axis == 0 ? (uint32_t)(idx * k + j0) : (uint32_t)(j0 * k + idx)) : kParityRef;
-  const uint32_t ref1 = q01 ? (axis == 0 ? (uint32_t)(idx * k + j1) : (uint32_t)(j1 * k + idx)) : kParityRef;
+  const uint32_t ref0 = q00 ? (axis == 0 ? (idx << lk) + j0 : (j0 << lk) + idx) : kParityRef;
+  const uint32_t ref1 = q01 ? (axis == 0 ? (idx << lk) + j1 : (j1 << lk) + idx) : kParityRef;
   uint32_t nl[8], nr[8], dl[8], dr[8];
   ns_by_ref(ns_sq, ref0, nl);
   ns_by_ref(ns_sq, ref1, nr);
-  load_digest(dig + cell0 * kDigest, dl);
-  load_digest(dig + cell1 * kDigest, dr);
+  load_digest(dig_u + c0, dl);
+  load_digest(dig_u + c1, dr);
   if (q01) {  // nmt Push order: ns(j0) <= ns(j1) <= ns(j1+1)
     bool bad = ns_less(nr, nl);
     if (j1 + 1 < k) {
-      const uint32_t ref2 = axis == 0 ? (uint32_t)(idx * k + j1 + 1) : (uint32_t)((j1 + 1) * k + idx);
+      const uint32_t ref2 = axis == 0 ? (idx << lk) + j1 + 1 : ((j1 + 1) << lk) + idx;
       uint32_t n2[8];
       ns_by_ref(ns_sq, ref2, n2);
       bad |= ns_less(n2, nr);
@@ -195,12 +189,12 @@ __global__ __launch_bounds__(256) void nmt_level1_kernel(SquareArgs a, uint8_t* 
 #pragma unroll
   for (int i = 0; i < 8; i++) dg[i] = bswap32(st[i]);
   if (final_level) {
-    uint8_t* dst = (axis == 0 ? a.row_roots : a.col_roots) + (sq * w + idx) * kNodeSize;
-    write_root(dst, nl, rpar ? nl : nr, dg);
+    uint8_t* dst_u = (axis == 0 ? a.row_roots : a.col_roots) + (sq << m.lw) * kNodeSize;
+    write_root(dst_u + idx * (uint32_t)kNodeSize, nl, rpar ? nl : nr, dg);
   } else {
     const uint32_t lref = lpar ? kParityRef : ref0;
     const uint32_t rref = rpar ? kParityRef : ref1;
-    uint4* o = (uint4*)(out_rec + gid * 48);
+    uint4* o = (uint4*)(out_rec + level_out_u(blockIdx.x) * 48 + level_out_l(threadIdx.x) * 48u);
     o[0] = make_uint4(dg[0], dg[1], dg[2], dg[3]);
     o[1] = make_uint4(dg[4], dg[5], dg[6], dg[7]);
     o[2] = make_uint4(lref, rref == kParityRef ? lref : rref, 0u, 0u);
@@ -208,20 +202,17 @@ __global__ __launch_bounds__(256) void nmt_level1_kernel(SquareArgs a, uint8_t* 
 }
 
 // Levels >= 2: node q of tree t from records 2q, 2q+1 of the previous level.
-__global__ __launch_bounds__(256) void nmt_level_kernel(SquareArgs a, const uint8_t* in_rec, uint8_t* out_rec,
-                                                        int level, int final_level) {
-  const int k = a.k;
-  const int w = 2 * k;
-  const int per = w >> level;  // nodes per tree at this level
-  const long gid = (long)blockIdx.x * 256 + threadIdx.x;
-  const long total = a.nsq * 2L * w * per;
-  if (gid >= total) return;
-  long sq;
-  int axis, idx, p;
-  level_coords(gid, w, per, sq, axis, idx, p);
-  const uint8_t* ns_sq = a.ns_table + sq * (long)k * k * 32;
-  const uint4* li = (const uint4*)(in_rec + level_rec(sq, w, 2 * per, axis, idx, 2 * p) * 48);
-  const uint4* ri = (const uint4*)(in_rec + level_rec(sq, w, 2 * per, axis, idx, 2 * p + 1) * 48);
+template <bool kWide>
+__global__ __launch_bounds__(256) void nmt_level_kernel(SquareArgs a, LevelMap m, const uint8_t* in_rec,
+                                                        uint8_t* out_rec, int final_level) {
+  const LevelNode n = level_node<kWide>(m, blockIdx.x, threadIdx.x);
+  if (!n.valid) return;
+  const long sq = n.sq;
+  const uint8_t* ns_sq = a.ns_table + (sq << (2 * m.lw + 3));  // k^2 entries of 32 B
+  const uint8_t* in_u = in_rec + level_child_u(m, n, false) * 48;
+  const uint32_t c0 = level_child_l(m, n) * 48u;
+  const uint4* li = (const uint4*)(in_u + c0);
+  const uint4* ri = (const uint4*)(in_u + (c0 + level_child_step(m, n) * 48u));
   const uint4 l0 = li[0], l1 = li[1], l2 = li[2], r0 = ri[0], r1 = ri[1], r2 = ri[2];
   const uint32_t dl[8] = {l0.x, l0.y, l0.z, l0.w, l1.x, l1.y, l1.z, l1.w};
   const uint32_t dr[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
@@ -256,11 +247,12 @@ __global__ __launch_bounds__(256) void nmt_level_kernel(SquareArgs a, const uint
   for (int i = 0; i < 8; i++) dg[i] = bswap32(st[i]);
   const bool rpar = r2.x == kParityRef;
   if (final_level) {
-    uint8_t* dst = (axis == 0 ? a.row_roots : a.col_roots) + (sq * w + idx) * kNodeSize;
+    uint8_t* dst_u = (n.axis == 0 ? a.row_roots : a.col_roots) + (sq << m.lw) * kNodeSize;
+    uint8_t* dst = dst_u + level_tree(m, n) * (uint32_t)kNodeSize;
     if (rpar) write_root(dst, lmn, lmx, dg);
     else write_root(dst, lmn, rmx, dg);
   } else {
-    uint4* o = (uint4*)(out_rec + gid * 48);
+    uint4* o = (uint4*)(out_rec + level_out_u(blockIdx.x) * 48 + level_out_l(threadIdx.x) * 48u);
     o[0] = make_uint4(dg[0], dg[1], dg[2], dg[3]);
     o[1] = make_uint4(dg[4], dg[5], dg[6], dg[7]);
     o[2] = make_uint4(l2.x, rpar ? l2.y : r2.y, 0u, 0u);
@@ -438,27 +430,33 @@ hipError_t launch_nmt_leaves(const SquareArgs& a, hipStream_t s, int row0, int n
   if (nrows < 0) nrows = (int)w - row0;
   if (row0 < 0 || nrows <= 0 || row0 + nrows > w || (zero_status && (row0 != 0 || !a.status)))
     return hipErrorInvalidValue;
-  const long total = nrows * w * a.nsq;
-  const long blocks = (total + kLeafWave - 1) / kLeafWave;
-  hipLaunchKernelGGL(nmt_leaf_kernel, dim3((unsigned)blocks), dim3(kLeafWave), 0, s, a, row0, nrows,
-                     (int)zero_status);
+  LeafMap m;  // refuses a k that is no power of two
+  if (!leaf_map(a.k, a.nsq, row0, nrows, m)) return hipErrorInvalidValue;
+  const long blocks = leaf_blocks(m);
+  if (blocks > kNmtMaxBlocks) return hipErrorInvalidValue;
+  const auto kern = leaf_wide(m) ? nmt_leaf_kernel<true> : nmt_leaf_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kLeafWave), 0, s, a, m, (int)zero_status);
   return hipGetLastError();
 }
 
 hipError_t launch_nmt_tree_levels(const SquareArgs& a, int first, int last, uint8_t* const pp[2], uint8_t* last_out,
                                   hipStream_t s) {
-  const int w = 2 * a.k;
   const int levels = nmt_levels(a.k);
   if (first < 1 || last > levels || first > last) return hipErrorInvalidValue;
   for (int L = first; L <= last; L++) {
     const uint8_t* in = pp[(L - first) & 1];
     uint8_t* out = L == last && last_out ? last_out : pp[(L - first + 1) & 1];
-    const long total = a.nsq * 2L * w * (w >> L);
-    const dim3 grid((unsigned)((total + 255) / 256));
-    if (L == 1)
-      hipLaunchKernelGGL(nmt_level1_kernel, grid, dim3(256), 0, s, a, out, (int)(levels == 1));
-    else
-      hipLaunchKernelGGL(nmt_level_kernel, grid, dim3(256), 0, s, a, in, out, L, (int)(L == levels));
+    LevelMap m;  // refuses a k that is no power of two
+    if (!level_map(a.k, a.nsq, L, m) || level_blocks(m) > kNmtMaxBlocks) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)level_blocks(m));
+    const bool wide = level_wide(m);
+    if (L == 1) {
+      const auto kern = wide ? nmt_level1_kernel<true> : nmt_level1_kernel<false>;
+      hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, a, m, out, (int)(levels == 1));
+    } else {
+      const auto kern = wide ? nmt_level_kernel<true> : nmt_level_kernel<false>;
+      hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, a, m, in, out, (int)(L == levels));
+    }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
@@ -476,7 +474,7 @@ long nmt_level_fill_blocks() {
     int dev = 0, cus = 0, per_cu = 0;
     if (hipGetDevice(&dev) != hipSuccess ||
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nmt_level_kernel, 256, 0) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, nmt_level_kernel<true>, 256, 0) != hipSuccess ||
         cus <= 0 || per_cu <= 0) {
       (void)hipGetLastError();
       return 0L;  // unknown: defer nothing
