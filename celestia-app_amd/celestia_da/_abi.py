@@ -81,6 +81,10 @@ EXPORTS = (
     "dagpu_blob_commitments_workspace_size",
     "dagpu_blob_commitments_device",
     "dagpu_square_plan_blobs",
+    "dagpu_blob_tx_check",
+    "dagpu_blob_tx_validate_workspace_size",
+    "dagpu_blob_tx_validate_device",
+    "dagpu_blob_tx_validate_host",
     "dagpu_square_scan_workspace_size",
     "dagpu_square_scan_device",
     "dagpu_square_scan_host",
@@ -143,6 +147,10 @@ COMMIT_PUSH_ORDER = 2
 PLAN_OK, PLAN_NO_SPACE_TX, PLAN_NO_SPACE_BLOB_TX, PLAN_TX_AFTER_BLOB_TX = 0, 1, 2, 3
 PLAN_LAYOUT, PLAN_TOO_MANY_BLOBS, PLAN_WIDTH, PLAN_ARENA = 4, 5, 6, 7
 PLAN_RECORD_BYTES = 32
+# dagpu_blob_tx_check / dagpu_blob_tx_validate_*: status word = kind | index << 8
+# (DAGPU_BLOBTX_*; the names are blobtx.KIND_NAMES)
+BLOBTX_KINDS = 25
+BLOBTX_NONE = 0xFFFFFFFF
 # dagpu_square_scan_device / dagpu_square_read_device (include/dagpu.h)
 SCAN_OK, SCAN_NAMESPACE, SCAN_INCONSISTENT, SCAN_LENGTH, SCAN_OVERFLOW = 0, 1, 2, 3, 4
 SCAN_SUMMARY_WORDS = 8
@@ -286,6 +294,12 @@ def lib() -> ctypes.CDLL:
         L.dagpu_blob_commitments_device.argtypes = [vp, ctypes.c_uint32, sz, sz, vp, vp, sz, sz, ctypes.c_uint32, vp, vp,
                                                     vp, vp, vp, vp]
         L.dagpu_square_plan_blobs.argtypes = [vp, sz, vp, sz, ctypes.POINTER(sz)]
+        L.dagpu_blob_tx_check.argtypes = [vp, sz]
+        L.dagpu_blob_tx_check.restype = ctypes.c_uint32
+        L.dagpu_blob_tx_validate_workspace_size.argtypes = [sz, sz, sz]
+        L.dagpu_blob_tx_validate_workspace_size.restype = sz
+        L.dagpu_blob_tx_validate_device.argtypes = [vp, sz, vp, vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp]
+        L.dagpu_blob_tx_validate_host.argtypes = [sz, vp, vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp]
         u32 = ctypes.c_uint32
         L.dagpu_square_scan_workspace_size.argtypes = [u32, sz]
         L.dagpu_square_scan_workspace_size.restype = sz

@@ -213,9 +213,11 @@ URL_MSG_PAY_FOR_BLOBS = "/celestia.blob.v1.MsgPayForBlobs"
 class BlobTxError(ValueError):
     """A ValidateBlobTx failure; `name` is the reference's error name."""
 
-    def __init__(self, name: str, msg: str):
+    def __init__(self, name: str, msg: str, kind: str = "", index: int = 0):
         super().__init__(f"{name}: {msg}")
         self.name = name
+        # validate_blob_tx: the kind of KIND_NAMES and the index the native word carries
+        self.kind, self.index = kind, index
 
 
 @dataclass
@@ -362,3 +364,214 @@ def blob_data_offsets(raw_blob_tx: bytes) -> List[Tuple[int, int]]:
             out.append(found)
         i += n
     return out
+
+
+# ---- ValidateBlobTx, the stateless rules (x/blob/types/blob_tx.go:36-103) -----------------------
+# The readable mirror of csrc/blobtx_check.hpp, written independently of it: the same rules in
+# the same order over the decoded objects.  The native per-tx word is kind | index << 8
+# (dagpu_blob_tx_check, include/dagpu.h DAGPU_BLOBTX_*).
+
+KIND_NAMES = (
+    "OK", "DECODE", "MULTIPLE_MSGS", "NO_PFB", "PFB_DECODE", "NO_NAMESPACES", "NO_SHARE_VERSIONS",
+    "NO_BLOB_SIZES", "NO_SHARE_COMMITMENTS", "MISMATCHED_COUNTS", "INVALID_NAMESPACE", "RESERVED_NAMESPACE",
+    "INVALID_NAMESPACE_VERSION", "UNSUPPORTED_SHARE_VERSION", "BAD_SIGNER", "BAD_COMMITMENT_LENGTH",
+    "BLOB_NAMESPACE_VERSION_TOO_LARGE", "BLOB_INVALID_NAMESPACE", "BLOB_RESERVED_NAMESPACE",
+    "BLOB_INVALID_NAMESPACE_VERSION", "ZERO_BLOB_SIZE", "BLOB_UNSUPPORTED_SHARE_VERSION", "SIZE_MISMATCH",
+    "NAMESPACE_MISMATCH", "NON_BLOB_TX_HAS_PFB")
+
+# kind -> the reference's error (x/blob/types/errors.go), or what stands in for one it takes from
+# elsewhere: the TxDecoder's and the unpacker's errors, bech32's, fmt.Errorf at payforblob.go:218
+# and namespace.New's
+_ERR_OF = {
+    "DECODE": "ErrTxDecode", "MULTIPLE_MSGS": "ErrMultipleMsgsInBlobTx", "NO_PFB": "ErrNoPFB",
+    "PFB_DECODE": "ErrTxDecode", "NO_NAMESPACES": "ErrNoNamespaces", "NO_SHARE_VERSIONS": "ErrNoShareVersions",
+    "NO_BLOB_SIZES": "ErrNoBlobSizes", "NO_SHARE_COMMITMENTS": "ErrNoShareCommitments",
+    "MISMATCHED_COUNTS": "ErrMismatchedNumberOfPFBComponent", "INVALID_NAMESPACE": "ErrInvalidNamespace",
+    "RESERVED_NAMESPACE": "ErrReservedNamespace", "INVALID_NAMESPACE_VERSION": "ErrInvalidNamespaceVersion",
+    "UNSUPPORTED_SHARE_VERSION": "ErrUnsupportedShareVersion", "BAD_SIGNER": "ErrInvalidAddress",
+    "BAD_COMMITMENT_LENGTH": "ErrInvalidShareCommitment",
+    "BLOB_NAMESPACE_VERSION_TOO_LARGE": "namespace version is too large",
+    "BLOB_INVALID_NAMESPACE": "unsupported namespace", "BLOB_RESERVED_NAMESPACE": "ErrReservedNamespace",
+    "BLOB_INVALID_NAMESPACE_VERSION": "ErrInvalidNamespaceVersion", "ZERO_BLOB_SIZE": "ErrZeroBlobSize",
+    "BLOB_UNSUPPORTED_SHARE_VERSION": "ErrUnsupportedShareVersion", "SIZE_MISMATCH": "ErrBlobSizeMismatch",
+    "NAMESPACE_MISMATCH": "ErrNamespaceMismatch", "NON_BLOB_TX_HAS_PFB": "tx has PFB but is not a blob tx",
+}
+
+
+def error_name(kind: int) -> str:
+    """The reference's error for a kind of KIND_NAMES (see _ERR_OF)."""
+    return _ERR_OF[KIND_NAMES[kind]]
+
+
+BECH32_CHARSET = "qpzry9x8gf2tvdw0s3jn54khce6mua7l"
+ACCOUNT_HRP = "celestia"
+
+
+def _fail(kind: str, index: int = 0, msg: str = ""):
+    return BlobTxError(_ERR_OF[kind], msg or kind, kind=kind, index=min(index, (1 << 24) - 1))
+
+
+def _bech32_polymod(values) -> int:
+    chk = 1
+    for v in values:
+        top = chk >> 25
+        chk = ((chk & 0x1FFFFFF) << 5) ^ v
+        for i, g in enumerate((0x3B6A57B2, 0x26508E6D, 0x1EA119FA, 0x3D4233DD, 0x2A1462B3)):
+            if (top >> i) & 1:
+                chk ^= g
+    return chk
+
+
+def bech32_decode(addr: str) -> Tuple[str, bytes]:
+    """BIP-173 bech32 as sdk.AccAddressFromBech32 uses it: (hrp, the data
+    regrouped from 5 to 8 bits without padding).  Raises ValueError.  The SDK
+    is not vendored in the reference: recalled, parity unpinned beyond the
+    addresses the reference's own files contain."""
+    if any(ord(c) < 33 or ord(c) > 126 for c in addr):
+        raise ValueError("bech32: character out of range")
+    if addr.lower() != addr and addr.upper() != addr:
+        raise ValueError("bech32: mixed case")
+    addr = addr.lower()
+    sep = addr.rfind("1")
+    if sep < 1 or len(addr) - sep - 1 < 6:
+        raise ValueError("bech32: separator")
+    hrp, data = addr[:sep], []
+    for c in addr[sep + 1:]:
+        v = BECH32_CHARSET.find(c)
+        if v < 0:
+            raise ValueError(f"bech32: invalid character {c!r}")
+        data.append(v)
+    if _bech32_polymod([ord(c) >> 5 for c in hrp] + [0] + [ord(c) & 31 for c in hrp] + data) != 1:
+        raise ValueError("bech32: checksum")
+    acc = bits = 0
+    out = bytearray()
+    for v in data[:-6]:
+        acc = (acc << 5) | v
+        bits += 5
+        if bits >= 8:
+            bits -= 8
+            out.append((acc >> bits) & 0xFF)
+    if bits >= 5 or acc & ((1 << bits) - 1):
+        raise ValueError("bech32: padding")
+    return hrp, bytes(out)
+
+
+def acc_address_from_bech32(signer: str) -> bytes:
+    """sdk.AccAddressFromBech32 with the prefix "celestia" (see bech32_decode)."""
+    if not signer.strip(" "):
+        raise ValueError("empty address string is not allowed")
+    hrp, raw = bech32_decode(signer)
+    if hrp != ACCOUNT_HRP:
+        raise ValueError(f"invalid Bech32 prefix; expected {ACCOUNT_HRP}, got {hrp}")
+    if not 1 <= len(raw) <= 255:
+        raise ValueError("address length")
+    return raw
+
+
+def _namespace_rule(ns: bytes) -> str:
+    """namespace.From / New, then ValidateBlobNamespace (payforblob.go:183-193):
+    "" or INVALID_NAMESPACE / RESERVED_NAMESPACE / INVALID_NAMESPACE_VERSION."""
+    if len(ns) != 29 or ns[0] not in (0, 255) or (ns[0] == 0 and any(ns[1:19])):
+        return "INVALID_NAMESPACE"
+    if ns <= bytes(28) + b"\xff" or ns >= b"\xff" * 28 + b"\x00":
+        return "RESERVED_NAMESPACE"
+    return "" if ns[0] == 0 else "INVALID_NAMESPACE_VERSION"
+
+
+def validate_blob_tx(raw: bytes) -> None:
+    """ValidateBlobTx short of the comparison of the commitments themselves
+    (blob_tx.go:92-100; check_commitments makes it on the device): raises
+    BlobTxError for the first rule `raw`, a BlobTx, breaks, with the
+    reference's error name and .kind / .index as the native word carries them.
+    ValueError when raw is no BlobTx."""
+    t, ok = unmarshal_blob_tx(bytes(raw))
+    if not ok:
+        raise ValueError("not a BlobTx")
+    try:
+        msgs = sdk_tx_messages(t.tx)
+    except ProtoError as e:
+        raise _fail("DECODE", 0, str(e))
+    if len(msgs) != 1:
+        raise _fail("MULTIPLE_MSGS", len(msgs), f"{len(msgs)} sdk.Msgs found in BlobTx")
+    if msgs[0][0] != URL_MSG_PAY_FOR_BLOBS:
+        raise _fail("NO_PFB")
+    try:
+        pfb = unmarshal_msg_pay_for_blobs(msgs[0][1])
+    except ProtoError as e:
+        raise _fail("PFB_DECODE", 0, str(e))
+    # MsgPayForBlobs.ValidateBasic (payforblob.go:95-148)
+    if not pfb.namespaces:
+        raise _fail("NO_NAMESPACES")
+    if not pfb.share_versions:
+        raise _fail("NO_SHARE_VERSIONS")
+    if not pfb.blob_sizes:
+        raise _fail("NO_BLOB_SIZES")
+    if not pfb.share_commitments:
+        raise _fail("NO_SHARE_COMMITMENTS")
+    if not len(pfb.namespaces) == len(pfb.share_versions) == len(pfb.blob_sizes) == len(pfb.share_commitments):
+        raise _fail("MISMATCHED_COUNTS")
+    for i, ns in enumerate(pfb.namespaces):
+        rule = _namespace_rule(ns)
+        if rule:
+            raise _fail(rule, i)
+    for i, v in enumerate(pfb.share_versions):
+        if v != 0:
+            raise _fail("UNSUPPORTED_SHARE_VERSION", i)
+    try:
+        acc_address_from_bech32(pfb.signer)
+    except ValueError as e:
+        raise _fail("BAD_SIGNER", 0, str(e))
+    for i, c in enumerate(pfb.share_commitments):
+        if len(c) != 32:
+            raise _fail("BAD_COMMITMENT_LENGTH", i)
+    # ValidateBlobs (payforblob.go:211-239)
+    for i, b in enumerate(t.blobs):
+        if b.namespace_version > 255:
+            raise _fail("BLOB_NAMESPACE_VERSION_TOO_LARGE", i)
+        rule = _namespace_rule(bytes([b.namespace_version]) + b.namespace_id)
+        if rule:
+            raise _fail("BLOB_" + rule, i)
+        if len(b.data) == 0:
+            raise _fail("ZERO_BLOB_SIZE", i)
+        if b.share_version & 0xFF != 0:
+            raise _fail("BLOB_UNSUPPORTED_SHARE_VERSION", i)
+    sizes = [len(b.data) for b in t.blobs]
+    if len(sizes) != len(pfb.blob_sizes):
+        raise _fail("SIZE_MISMATCH", min(len(sizes), len(pfb.blob_sizes)))
+    for i, (got, declared) in enumerate(zip(sizes, pfb.blob_sizes)):
+        if got != declared:
+            raise _fail("SIZE_MISMATCH", i, f"actual {sizes} declared {pfb.blob_sizes}")
+    for i, ns in enumerate(pfb.namespaces):
+        if bytes([t.blobs[i].namespace_version]) + t.blobs[i].namespace_id != ns:
+            raise _fail("NAMESPACE_MISMATCH", i)
+
+
+def check_tx(raw: bytes) -> Tuple[int, int]:
+    """(kind, index) of any tx as ProcessProposal's loop sees it
+    (process_proposal.go:60-77, :120), from the mirror: validate_blob_tx for a
+    BlobTx; for any other tx NON_BLOB_TX_HAS_PFB with the first such message
+    when it decodes and holds a MsgPayForBlobs, else (0, 0)."""
+    raw = bytes(raw)
+    if unmarshal_blob_tx(raw)[1]:
+        try:
+            validate_blob_tx(raw)
+        except BlobTxError as e:
+            return KIND_NAMES.index(e.kind), e.index
+        return 0, 0
+    try:
+        urls = [u for u, _ in sdk_tx_messages(raw)]
+    except ProtoError:
+        return 0, 0
+    if URL_MSG_PAY_FOR_BLOBS in urls:
+        return KIND_NAMES.index("NON_BLOB_TX_HAS_PFB"), min(urls.index(URL_MSG_PAY_FOR_BLOBS), (1 << 24) - 1)
+    return 0, 0
+
+
+def check_native(raw: bytes) -> Tuple[int, int]:
+    """(kind, index) of one tx through dagpu_blob_tx_check (csrc/blobtx_check.hpp)."""
+    import numpy as np
+
+    from . import _abi
+    buf = np.frombuffer(bytes(raw), np.uint8)
+    word = _abi.lib().dagpu_blob_tx_check(_abi.addr(buf) if buf.size else None, buf.size)
+    return word & 0xFF, word >> 8

@@ -582,6 +582,9 @@ class PlannedSquares:
         self.n, self.arena, self.records, self.status = n, arena, records, status
         self.src, self.src_lens, self._stream = src, src_lens, stream
         self._rec = self._plans = None
+        # the request as the planner took it (host arrays), for validate_blob_txs_device
+        self.src_offs = self.ntx = self.tx_lens = None
+        self.src_bytes = self.arena_cap = 0
 
     def status_host(self):
         """The n status words: the one read a caller needs to go on."""
@@ -671,7 +674,56 @@ def plan_squares_device(blocks, max_square_size: int = 128, threshold: int = 64,
     # only for work queued on the same stream behind them
     del host
     p = PlannedSquares(n, arena, records, status, d_src, [int(offs[i + 1] - offs[i]) for i in range(n)], s)
+    p.src_offs, p.ntx, p.tx_lens, p.src_bytes, p.arena_cap = offs, ntx, lens, total, cap
     return p
+
+
+def validate_blob_txs_device(planned: PlannedSquares, blob_base="plans", ctx: Optional[Context] = None,
+                             stream: Optional[torch.cuda.Stream] = None):
+    """dagpu_blob_tx_validate_device over the txs plan_squares_device left in
+    HBM: the stateless rules of ValidateBlobTx on every tx where it lies, and
+    the table of the commitments the MsgPayForBlobs declare.
+
+    blob_base: (n + 1,) uint64-like on the HOST, block i's plan blobs own rows
+    [blob_base[i], blob_base[i + 1]) of the table; "plans" (the default) takes
+    each accepted block's blob count from the planner's records (one small
+    read), which is DeviceSquares.blob_table()'s order; None ties nothing.
+    Returns cuda tensors (tx_status (ntx_total,) int32, block_status (n, 2)
+    int32 {lowest failing tx or -1, its word}, expected (rows, 32) uint8); a
+    word is kind | index << 8 (blobtx.KIND_NAMES).  Enqueued on `stream`: it
+    does not synchronise."""
+    import numpy as np
+    c = ctx or default_context()
+    n, dev = planned.n, planned.src.device
+    if planned.src_offs is None:
+        raise ValueError("planned carries no request: it must come from plan_squares_device")
+    if isinstance(blob_base, str):
+        if blob_base != "plans":
+            raise ValueError("blob_base is an array, None or 'plans'")
+        rec = planned.records_host()
+        counts = np.where(rec["plan_bytes"] == 0, 0, rec["nblob"]).astype(np.uint64)
+        blob_base = np.concatenate([np.zeros(1, np.uint64), np.cumsum(counts, dtype=np.uint64)])
+    elif blob_base is not None:
+        blob_base = np.ascontiguousarray(np.asarray(blob_base, dtype=np.uint64).reshape(-1))
+        if blob_base.size != n + 1:
+            raise ValueError("blob_base holds n + 1 offsets")
+    rows = int(blob_base[n]) if blob_base is not None and n else 0
+    ntx_total = int(planned.tx_lens.size)
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.stream(s):
+        tx_status = torch.empty((max(ntx_total, 1),), dtype=torch.int32, device=dev)
+        block_status = torch.empty((max(n, 1), 2), dtype=torch.int32, device=dev)
+        expected = torch.empty((max(rows, 1), 32), dtype=torch.uint8, device=dev)
+        ws = torch.empty((max(c._L.dagpu_blob_tx_validate_workspace_size(n, ntx_total, rows), 16),),
+                         dtype=torch.uint8, device=dev)
+    rc = c._L.dagpu_blob_tx_validate_device(
+        c.handle, n, _abi.addr(planned.src), _abi.addr(planned.src_offs), planned.src_bytes, _abi.addr(planned.ntx),
+        _abi.addr(planned.tx_lens) if ntx_total else None, _abi.addr(planned.arena), planned.arena_cap,
+        _abi.addr(planned.records), _abi.addr(blob_base), _abi.addr(tx_status), _abi.addr(block_status),
+        _abi.addr(expected), _abi.addr(ws), _stream_handle(s))
+    if rc != 0:
+        raise DAError(rc, c.last_error())
+    return tx_status[:ntx_total], block_status[:n], expected[:rows]
 
 
 def construct_squares_device(k: int, blocks, out: torch.Tensor, square_stride: int, row_pitch: int,
@@ -914,6 +966,11 @@ class DeviceSquares:
         # blob_table / check_commitments
         self._plans = None
         self._src_lens = None
+        # load_txs(plan="device"): what the planner left in HBM (PlannedSquares), and
+        # validate_blob_txs()'s (tx_status, block_status, expected) over it
+        self._planned = self._validated = None
+        # extend() / roots() have filled self.dah for the squares now loaded
+        self._dah_ready = False
         # scan(): (records, summary, host summary, (buffer, square_stride, row_pitch))
         self._scan = None
         # proof_store(): the ProofStore of self.eds, until the squares change;
@@ -929,6 +986,8 @@ class DeviceSquares:
         """Copy n ODS (anything viewable as (n, k*k*512) uint8) to where extend()
         reads them: self.ods, or Q0 of the EDS when in_place."""
         self._proof_store = self._tx_index = None
+        self._planned = self._validated = None
+        self._dah_ready = False
         src = ods if isinstance(ods, torch.Tensor) else torch.from_numpy(ods)
         src = src.reshape(self.n, self.k, self.k * 512)
         if self.in_place:
@@ -961,6 +1020,8 @@ class DeviceSquares:
         if len(blocks) != self.n:
             raise ValueError(f"{self.n} blocks expected, got {len(blocks)}")
         self._proof_store = self._tx_index = None
+        self._planned = self._validated = None
+        self._dah_ready = False
         if self.ods is None and not self.in_place:
             raise ValueError("no ODS buffer: DeviceSquares(with_ods=False) takes its input through extend_from")
         m = sq.SQUARE_SIZE_UPPER_BOUND if max_square_size is None else max_square_size
@@ -1014,6 +1075,7 @@ class DeviceSquares:
                 raise DAError(_abi.ERR_ARG, f"block {i} has square width {index}, these squares have width {self.k}")
         self._plans = p  # downloaded by _host_plans when first asked for
         self._src_lens = p.src_lens
+        self._planned = p
 
     def _host_plans(self):
         if isinstance(self._plans, PlannedSquares):
@@ -1045,8 +1107,14 @@ class DeviceSquares:
         extend(), which never changes Q0), compared on the device with
         `expected` ((nblobs, 32), in blob_table order) when given.  Returns
         blob_commitments_device's (commitments, status, square_status), enqueued
-        on `stream`: one read of square_status tells which blocks to reject."""
+        on `stream`: one read of square_status tells which blocks to reject.
+        expected="declared": the table validate_blob_txs() filled on the device
+        from the blocks' MsgPayForBlobs (it runs first if it has not run)."""
         from . import square as sq
+        if isinstance(expected, str):
+            if expected != "declared":
+                raise ValueError("expected is a (nblobs, 32) table, None or 'declared'")
+            expected = (self._validated or self.validate_blob_txs(stream=stream))[2]
         rec, _ = self.blob_table()
         w = 2 * self.k
         buf, stride, pitch = ((self.eds, w * w * 512, w * 512) if self.in_place
@@ -1054,6 +1122,70 @@ class DeviceSquares:
         return blob_commitments_device(self.k, rec, buf.view(-1), stride, pitch, expected=expected,
                                        threshold=sq.SUBTREE_ROOT_THRESHOLD if threshold is None else threshold,
                                        ctx=self.ctx, stream=stream)
+
+    # ---- ValidateBlobTx (dagpu_blob_tx_validate_device) and ProcessProposal's verdict ----
+
+    def validate_blob_txs(self, stream: Optional[torch.cuda.Stream] = None):
+        """The stateless rules of ValidateBlobTx over every tx of the batch
+        load_txs(plan="device") left in HBM, and the commitments their
+        MsgPayForBlobs declare in blob_table() order: validate_blob_txs_device's
+        (tx_status, block_status, expected), enqueued on `stream` and kept for
+        check_commitments(expected="declared") / process_proposals()."""
+        if self._planned is None:
+            raise ValueError("the txs are not resident in HBM: validate_blob_txs follows load_txs(plan='device'); "
+                             "the host-plan route uploads no raw txs the device could walk")
+        self._validated = validate_blob_txs_device(self._planned, ctx=self.ctx, stream=stream)
+        return self._validated
+
+    def process_proposals(self, data_hashes=None, stream: Optional[torch.cuda.Stream] = None):
+        """The data-parallel part of ProcessProposal (app/process_proposal.go:53-164)
+        for every block of the batch: [(accept, reason)], reason "" for an
+        accepted block.  Composes the planner's status, validate_blob_txs()'s
+        block words and check_commitments(expected="declared")'s square status
+        (each runs here if it has not), and, when data_hashes ((n, 32) bytes)
+        is given, extend()'s / roots()'s data roots against them; the
+        per-block words come back in one read.  A block's first reason in this
+        order is reported, with the reference's log strings; the reference
+        would name the tx of a commitment mismatch, which the square status
+        does not carry.  Signatures, the ante handler and upgrade messages are
+        not checked."""
+        import numpy as np
+
+        from . import blobtx as btx
+        s = stream if stream is not None else torch.cuda.current_stream(self.eds.device)
+        if self._planned is None:
+            raise ValueError("the txs are not resident in HBM: process_proposals follows load_txs(plan='device')")
+        _, block_status, _ = self._validated or self.validate_blob_txs(stream=s)
+        _, _, sq_status = self.check_commitments(expected="declared", stream=s)
+        with torch.cuda.stream(s):
+            words = [self._planned.status[:self.n].view(self.n, 1), block_status, sq_status[:self.n].view(self.n, 1)]
+            if data_hashes is not None:
+                if not self._dah_ready:
+                    raise ValueError("data_hashes given before extend() or roots() computed the data roots")
+                want = np.frombuffer(b"".join(bytes(h) for h in data_hashes), np.uint8).copy()
+                if want.size != 32 * self.n:
+                    raise ValueError("data_hashes holds 32 bytes per block")
+                want = torch.from_numpy(want.reshape(self.n, 32)).to(self.dah.device, non_blocking=True)
+                words.append((self.dah != want).any(dim=1).to(torch.int32).view(self.n, 1))
+            host = torch.cat(words, dim=1).cpu().numpy().view(np.uint32)
+        pfb_kind = btx.KIND_NAMES.index("NON_BLOB_TX_HAS_PFB")
+        out = []
+        for plan, tx, word, commit, *root in host.tolist():
+            if plan:
+                out.append((False, "failure to compute data square from transactions:"))
+            elif tx != _abi.BLOBTX_NONE and word & 0xFF == pfb_kind:
+                out.append((False, f"tx {tx} has PFB but is not a blob tx"))
+            elif tx != _abi.BLOBTX_NONE:
+                out.append((False, f"invalid blob tx {tx}: {btx.error_name(word & 0xFF)}"))
+            elif commit & _abi.COMMIT_PUSH_ORDER:
+                out.append((False, "invalid blob tx: ErrCalculateCommitment"))
+            elif commit & _abi.COMMIT_MISMATCH:
+                out.append((False, "invalid blob tx: ErrInvalidShareCommitment"))
+            elif root and root[0]:
+                out.append((False, "proposed data root differs from calculated data root"))
+            else:
+                out.append((True, ""))
+        return out
 
     # ---- square read (dagpu_square_scan_device / dagpu_square_read_device) ----
 
@@ -1371,6 +1503,7 @@ class DeviceSquares:
     def extend(self, stream: Optional[torch.cuda.Stream] = None) -> None:
         """ODS -> EDS -> roots -> DAH, enqueued on `stream` (no sync)."""
         self._proof_store = self._tx_index = None
+        self._dah_ready = True
         L = self.ctx._L
         self._ck(L.dagpu_extend_batch_device(
             self.ctx.handle, self.k, self.n, _abi.addr(self.ods), _abi.addr(self.eds),
@@ -1461,6 +1594,7 @@ class DeviceSquares:
         return torch.empty((ws,), dtype=torch.uint8, device=self.eds.device)
 
     def roots(self, stream: Optional[torch.cuda.Stream] = None) -> None:
+        self._dah_ready = True
         self._ck(self.ctx._L.dagpu_roots_device(
             self.ctx.handle, self.k, self.n, _abi.addr(self.eds), _abi.addr(self.row_roots),
             _abi.addr(self.col_roots), _abi.addr(self.dah), _abi.addr(self.status),

@@ -75,6 +75,7 @@ struct SpDeviceLanes {
 };
 
 // the host's checks of one call; fills the upload (SpBlockIn[n] | SpTxIn[ntx])
+// through sp_tables (square_plan.hpp), which dagpu_blob_tx_validate_* share
 int sp_check(dagpu_ctx* ctx, size_t n, const void* src, const size_t* src_offs, size_t src_bytes, const uint32_t* ntx,
              const uint64_t* tx_lens, uint32_t max_square_size, uint32_t threshold, const void* plans,
              const void* records, const void* status, std::vector<uint8_t>& up, uint64_t& ntx_total) {
@@ -85,6 +86,13 @@ int sp_check(dagpu_ctx* ctx, size_t n, const void* src, const size_t* src_offs, 
   if (n >= ((size_t)1 << 24)) return set_err(ctx, DAGPU_ERR_ARG, "more than 2^24 blocks in one call");
   if (((uintptr_t)plans | (uintptr_t)records | (uintptr_t)status) & 15)
     return set_err(ctx, DAGPU_ERR_ARG, "d_plans, d_records and d_status must be 16-byte aligned");
+  return sp_tables(ctx, n, src, src_offs, src_bytes, ntx, tx_lens, max_square_size, up, ntx_total);
+}
+
+}  // namespace
+
+int sp_tables(dagpu_ctx* ctx, size_t n, const void* src, const size_t* src_offs, size_t src_bytes, const uint32_t* ntx,
+              const uint64_t* tx_lens, uint32_t max_square_size, std::vector<uint8_t>& up, uint64_t& ntx_total) {
   if (src_offs[n] > src_bytes) return set_err(ctx, DAGPU_ERR_ARG, "src_offs end past src_bytes");
   ntx_total = 0;
   for (size_t i = 0; i < n; i++) ntx_total += ntx[i];
@@ -114,6 +122,8 @@ int sp_check(dagpu_ctx* ctx, size_t n, const void* src, const size_t* src_offs, 
   }
   return DAGPU_OK;
 }
+
+namespace {
 
 SpArgs sp_args(uint8_t* ws, const uint8_t* src, size_t n, uint64_t ntx_total, uint32_t max_square_size,
                uint32_t threshold, uint8_t* plans, size_t plans_cap, void* records, uint32_t* status) {

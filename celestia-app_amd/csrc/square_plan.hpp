@@ -824,3 +824,16 @@ inline void sp_emulate(const SpArgs& a, uint64_t ntx_total, SpShared& s) {
 }
 
 }  // namespace dagpu
+
+// ---- the request tables of a batch (square_plan.hip) ------------------------------
+// The checks every call over n blocks of packed txs makes of src_offs, ntx and
+// tx_lens (ascending offsets inside src_bytes, the 2 GiB and 2^24 txs of a
+// block, lengths that add up to each block's span), with the messages of
+// dagpu_square_plan_device, and the upload they fill: SpBlockIn[n] | SpTxIn[ntx].
+// src_offs and ntx are not null; n < 2^24.  ctx may be null (host executors).
+#include <vector>
+struct dagpu_ctx;
+namespace dagpu {
+int sp_tables(dagpu_ctx* ctx, size_t n, const void* src, const size_t* src_offs, size_t src_bytes, const uint32_t* ntx,
+              const uint64_t* tx_lens, uint32_t max_square_size, std::vector<uint8_t>& up, uint64_t& ntx_total);
+}

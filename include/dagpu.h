@@ -1062,6 +1062,119 @@ int dagpu_blob_commitments_device(dagpu_ctx* ctx, uint32_t k, size_t n, size_t n
                                   void* d_workspace, void* stream);
 int dagpu_square_plan_blobs(const uint8_t* plan, size_t plan_bytes, uint32_t* out, size_t cap, size_t* nblob);
 
+/* ---- ValidateBlobTx on the device: PFB decode and the stateless rules ------
+ * The other half of what ProcessProposal does per tx before it builds the
+ * square (app/process_proposal.go:60-77, :120): the rules of ValidateBlobTx
+ * (x/blob/types/blob_tx.go:36-103) short of the comparison of the commitments
+ * (blob_tx.go:92-100), which dagpu_blob_commitments_device makes against the
+ * table of declared commitments this call fills.  One function per tx
+ * (csrc/blobtx_check.hpp, shared by the kernels of csrc/blobtx_check.hip and
+ * the host executor) returns a word kind | index << 8, the first failure in
+ * the reference's order:
+ *   a BlobTx (blob.UnmarshalBlobTx, pkg/blob/blob.go:56-90):
+ *   DECODE         the inner tx does not decode (blob_tx.go:37-40).  The SDK's
+ *                  TxDecoder is not in the reference: the rule is the project's
+ *                  walker (Tx 1 body -> TxBody 1 messages -> Any {1 type_url,
+ *                  2 value}; a malformed buffer or a wrong wire type on one of
+ *                  those four fields); the SDK's stricter rejections are not
+ *                  restated.
+ *   MULTIPLE_MSGS  message count != 1 (blob_tx.go:44-47); index = the count,
+ *                  capped at 2^24 - 1
+ *   NO_PFB         type_url is not /celestia.blob.v1.MsgPayForBlobs (:49-52)
+ *   PFB_DECODE     the message value is malformed, or a wrong wire type on its
+ *                  fields 1, 2, 3, 4 or 8 (repeated uint32 packed or not)
+ *   MsgPayForBlobs.ValidateBasic (x/blob/types/payforblob.go:95-148):
+ *   NO_NAMESPACES, NO_SHARE_VERSIONS, NO_BLOB_SIZES, NO_SHARE_COMMITMENTS
+ *                  (:96-110), MISMATCHED_COUNTS (:112-117)
+ *   INVALID_NAMESPACE (namespace.From, :120-123), RESERVED_NAMESPACE
+ *                  (IsReserved, :184; pkg/namespace/namespace.go:108-118),
+ *                  INVALID_NAMESPACE_VERSION (:188); index = the namespace
+ *   UNSUPPORTED_SHARE_VERSION (:130-134); index = the share version
+ *   BAD_SIGNER     sdk.AccAddressFromBech32 with the prefix "celestia"
+ *                  (:136-139): BIP-173 bech32, the 5 -> 8 bit regrouping without
+ *                  padding, 1 to 255 bytes.  The SDK is not vendored in the
+ *                  reference: recalled, parity unpinned beyond the addresses
+ *                  the reference's files contain.
+ *   BAD_COMMITMENT_LENGTH (:141-145); index = the commitment
+ *   ValidateBlobs (payforblob.go:211-239), index = the blob:
+ *   BLOB_NAMESPACE_VERSION_TOO_LARGE (:217), BLOB_INVALID_NAMESPACE (:220),
+ *   BLOB_RESERVED_NAMESPACE, BLOB_INVALID_NAMESPACE_VERSION (:224),
+ *   ZERO_BLOB_SIZE (:229), BLOB_UNSUPPORTED_SHARE_VERSION (:233)
+ *   SIZE_MISMATCH  blob_tx.go:69; index = the first blob whose len(data) is not
+ *                  blob_sizes[i], or the smaller count when the counts differ
+ *   NAMESPACE_MISMATCH  blob_tx.go:73-89; index = the lowest such blob
+ *   any other tx (process_proposal.go:60-77): 0 when it does not decode,
+ *   NON_BLOB_TX_HAS_PFB (:72-76) with index = the first message whose type_url
+ *   is the PFB url, else 0.
+ *
+ * dagpu_blob_tx_check: the word of one tx in host memory; never reads a byte
+ * at or past n.  n is below 2 GiB, the bound of a block's txs; a longer buffer
+ * is not walked and gives 0.
+ *
+ * dagpu_blob_tx_validate_device: the txs of n blocks as
+ * dagpu_square_plan_device takes them (d_src, HOST src_offs[n + 1], src_bytes,
+ * HOST ntx[n], HOST tx_lens) with its request checks and messages, the plan
+ * arena and records it left in HBM (d_plans, plans_cap, d_records), and HOST
+ * blob_base[n + 1]: block i's plan blobs own rows [blob_base[i],
+ * blob_base[i + 1]) of the expected table, block by block in plan order (the
+ * order of dagpu_square_plan_blobs; a block without a plan owns no rows).
+ * blob_base == NULL ties nothing: d_plans, d_records and d_expected are then
+ * not read.  Outputs, all DEVICE:
+ *   d_tx_status     one word per tx of the batch, in batch order
+ *   d_block_status  two words per block, 8-B aligned: {index in the block of
+ *                   its lowest failing tx, or 0xFFFFFFFF; that tx's word, or 0}
+ *   d_expected      32 bytes per row: the commitment the blob's MsgPayForBlobs
+ *                   declares, found through the plan blob's data_off; zeros
+ *                   for a row whose tx failed before its commitment lengths
+ *                   were checked, or that ties to no blob.  Every row is written.
+ * Three kernels on `stream`: one lane per tx, one per block, one per row.
+ * Checked before anything is enqueued (DAGPU_ERR_ARG and a message): null
+ * pointers, alignment, blob_base starting at 0 and ascending, and the planner's
+ * checks of src_offs / ntx / tx_lens.  d_workspace (16-B aligned,
+ * dagpu_blob_tx_validate_workspace_size(n, ntx_total, blob_base[n]) = 48 n +
+ * 32 ntx_total + 32 bytes at most) must stay valid until the kernels have run;
+ * the call returns once its tables have left host memory.  With NULL the
+ * library allocates it and waits.
+ *
+ * dagpu_blob_tx_validate_host: the same arguments and outputs in HOST memory,
+ * the same per-tx and per-row functions run as loops.  No context, no device. */
+#define DAGPU_BLOBTX_OK 0
+#define DAGPU_BLOBTX_DECODE 1
+#define DAGPU_BLOBTX_MULTIPLE_MSGS 2
+#define DAGPU_BLOBTX_NO_PFB 3
+#define DAGPU_BLOBTX_PFB_DECODE 4
+#define DAGPU_BLOBTX_NO_NAMESPACES 5
+#define DAGPU_BLOBTX_NO_SHARE_VERSIONS 6
+#define DAGPU_BLOBTX_NO_BLOB_SIZES 7
+#define DAGPU_BLOBTX_NO_SHARE_COMMITMENTS 8
+#define DAGPU_BLOBTX_MISMATCHED_COUNTS 9
+#define DAGPU_BLOBTX_INVALID_NAMESPACE 10
+#define DAGPU_BLOBTX_RESERVED_NAMESPACE 11
+#define DAGPU_BLOBTX_INVALID_NAMESPACE_VERSION 12
+#define DAGPU_BLOBTX_UNSUPPORTED_SHARE_VERSION 13
+#define DAGPU_BLOBTX_BAD_SIGNER 14
+#define DAGPU_BLOBTX_BAD_COMMITMENT_LENGTH 15
+#define DAGPU_BLOBTX_BLOB_NAMESPACE_VERSION_TOO_LARGE 16
+#define DAGPU_BLOBTX_BLOB_INVALID_NAMESPACE 17
+#define DAGPU_BLOBTX_BLOB_RESERVED_NAMESPACE 18
+#define DAGPU_BLOBTX_BLOB_INVALID_NAMESPACE_VERSION 19
+#define DAGPU_BLOBTX_ZERO_BLOB_SIZE 20
+#define DAGPU_BLOBTX_BLOB_UNSUPPORTED_SHARE_VERSION 21
+#define DAGPU_BLOBTX_SIZE_MISMATCH 22
+#define DAGPU_BLOBTX_NAMESPACE_MISMATCH 23
+#define DAGPU_BLOBTX_NON_BLOB_TX_HAS_PFB 24
+uint32_t dagpu_blob_tx_check(const uint8_t* tx, size_t n);
+size_t dagpu_blob_tx_validate_workspace_size(size_t n, size_t ntx_total, size_t nblobs_total);
+int dagpu_blob_tx_validate_device(dagpu_ctx* ctx, size_t n, const uint8_t* d_src, const size_t* src_offs,
+                                  size_t src_bytes, const uint32_t* ntx, const uint64_t* tx_lens,
+                                  const uint8_t* d_plans, size_t plans_cap, const void* d_records,
+                                  const uint64_t* blob_base /* HOST, n + 1, may be NULL */, uint32_t* d_tx_status,
+                                  uint32_t* d_block_status, uint8_t* d_expected, void* d_workspace, void* stream);
+int dagpu_blob_tx_validate_host(size_t n, const uint8_t* src, const size_t* src_offs, size_t src_bytes,
+                                const uint32_t* ntx, const uint64_t* tx_lens, const uint8_t* plans, size_t plans_cap,
+                                const void* records, const uint64_t* blob_base, uint32_t* tx_status,
+                                uint32_t* block_status, uint8_t* expected);
+
 /* ---- Square read: txs and blobs back out of squares resident in HBM -------
  * The opposite direction of dagpu_square_write_device: square.Deconstruct
  * (pkg/square/square.go:65-155) split into a scan of the shares
