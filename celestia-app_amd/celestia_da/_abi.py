@@ -85,6 +85,15 @@ EXPORTS = (
     "dagpu_blob_tx_validate_workspace_size",
     "dagpu_blob_tx_validate_device",
     "dagpu_blob_tx_validate_host",
+    "dagpu_commit_plan_table_words",
+    "dagpu_commit_plan_workspace_size",
+    "dagpu_commit_plan_device",
+    "dagpu_commit_plan_host",
+    "dagpu_proposal_check_workspace_size",
+    "dagpu_proposal_check_device",
+    "dagpu_proposal_verdict_workspace_size",
+    "dagpu_proposal_verdict_device",
+    "dagpu_proposal_verdict_host",
     "dagpu_square_scan_workspace_size",
     "dagpu_square_scan_device",
     "dagpu_square_scan_host",
@@ -151,6 +160,11 @@ PLAN_RECORD_BYTES = 32
 # (DAGPU_BLOBTX_*; the names are blobtx.KIND_NAMES)
 BLOBTX_KINDS = 25
 BLOBTX_NONE = 0xFFFFFFFF
+# dagpu_proposal_verdict_*: code of a block's record {code, tx, word, aux} (DAGPU_VERDICT_*)
+VERDICT_NAMES = ("ACCEPT", "NON_BLOB_TX_HAS_PFB", "INVALID_BLOB_TX", "CALCULATE_COMMITMENT",
+                 "INVALID_SHARE_COMMITMENT", "CONSTRUCT_FAILED", "SQUARE_SIZE_DIFFERS", "NOT_JUDGED", "EXTEND_FAILED",
+                 "DATA_ROOT_DIFFERS")
+COMMIT_COUNT_WORDS = 8
 # dagpu_square_scan_device / dagpu_square_read_device (include/dagpu.h)
 SCAN_OK, SCAN_NAMESPACE, SCAN_INCONSISTENT, SCAN_LENGTH, SCAN_OVERFLOW = 0, 1, 2, 3, 4
 SCAN_SUMMARY_WORDS = 8
@@ -301,6 +315,20 @@ def lib() -> ctypes.CDLL:
         L.dagpu_blob_tx_validate_device.argtypes = [vp, sz, vp, vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp]
         L.dagpu_blob_tx_validate_host.argtypes = [sz, vp, vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp]
         u32 = ctypes.c_uint32
+        L.dagpu_commit_plan_table_words.argtypes = [u32, sz]
+        L.dagpu_commit_plan_table_words.restype = sz
+        L.dagpu_commit_plan_workspace_size.argtypes = [u32, sz]
+        L.dagpu_commit_plan_workspace_size.restype = sz
+        L.dagpu_commit_plan_device.argtypes = [vp, u32, sz, vp, sz, vp, u32, vp, vp, vp, vp, vp]
+        L.dagpu_commit_plan_host.argtypes = [u32, sz, vp, sz, vp, u32, vp, vp, vp]
+        L.dagpu_proposal_check_workspace_size.argtypes = [u32, sz, sz]
+        L.dagpu_proposal_check_workspace_size.restype = sz
+        L.dagpu_proposal_check_device.argtypes = [vp, u32, sz, vp, vp, sz, vp, vp, vp, sz, vp, vp, sz, sz, u32] + \
+            [vp] * 11
+        L.dagpu_proposal_verdict_workspace_size.argtypes = [u32, sz, sz]
+        L.dagpu_proposal_verdict_workspace_size.restype = sz
+        L.dagpu_proposal_verdict_device.argtypes = [vp, u32, sz] + [vp] * 12
+        L.dagpu_proposal_verdict_host.argtypes = [u32, sz] + [vp] * 10
         L.dagpu_square_scan_workspace_size.argtypes = [u32, sz]
         L.dagpu_square_scan_workspace_size.restype = sz
         L.dagpu_square_scan_device.argtypes = [vp, u32, sz, vp, sz, sz, u32, vp, vp, vp, vp, vp]

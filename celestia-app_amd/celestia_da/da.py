@@ -512,3 +512,98 @@ def extend_batch(ods: np.ndarray, ks: Sequence[int], ctx: Optional[Context] = No
         crs.append(cr[off:off + w * ROOT_SIZE].reshape(w, ROOT_SIZE))
         off += w * ROOT_SIZE
     return eds, rrs, crs, dah[:n], status[:n]
+
+
+# ---- ProcessProposal's data-parallel part, one block, in the reference's order ----
+
+def verdict_reason(code: int, tx: int = 0, word: int = 0, aux: int = 0) -> str:
+    """The reference's log string (app/process_proposal.go) for a verdict record
+    {code, tx, word, aux} of dagpu_proposal_verdict_* (_abi.VERDICT_NAMES); ""
+    for an accept."""
+    from . import blobtx as btx
+    name = _abi.VERDICT_NAMES[code]
+    if name == "ACCEPT":
+        return ""
+    if name == "NON_BLOB_TX_HAS_PFB":
+        return f"tx {tx} has PFB but is not a blob tx"
+    if name == "INVALID_BLOB_TX":
+        return f"invalid blob tx {tx}: {btx.error_name(word & 0xFF)}"
+    if name == "CALCULATE_COMMITMENT":
+        return f"invalid blob tx {tx}: ErrCalculateCommitment"
+    if name == "INVALID_SHARE_COMMITMENT":
+        return f"invalid blob tx {tx}: ErrInvalidShareCommitment"
+    if name == "CONSTRUCT_FAILED":
+        return "failure to compute data square from transactions:"
+    if name == "SQUARE_SIZE_DIFFERS":
+        return "proposed square size differs from calculated square size"
+    if name == "NOT_JUDGED":
+        return "not judged: the block's square width is not the batch's"
+    if name == "EXTEND_FAILED":
+        return "failure to erasure the data square"
+    return "proposed data root differs from calculated data root"
+
+
+def _data_root_of(shares: Sequence[bytes]) -> bytes:
+    return new_data_availability_header(extend_shares(list(shares))).hash()
+
+
+def process_proposal(txs: Sequence[bytes], data_hash: Optional[bytes] = None, square_size: Optional[int] = None,
+                     create_commitment=None, data_root=None):
+    """The readable mirror of the data-parallel part of ProcessProposal
+    (app/process_proposal.go:53-164) for one block of raw txs, in the
+    reference's order: (accept, reason, (code, tx, word, aux)), the record as
+    dagpu_proposal_verdict_* writes it (word 0 where the mirror does not restate
+    the planner's status word).
+
+    The tx loop (:53-132): blobtx.check_tx's stateless rules, then for a BlobTx
+    the comparison of every declared commitment with create_commitment
+    (blob_tx.go:91-100); the first failing tx rejects.  Then square.construct
+    (:135), the proposed square size (:142) and the data root (:147-164).
+    Signatures, the ante handler and upgrade messages are not checked.
+    create_commitment(namespace, data) and data_root(list of share bytes)
+    default to trees.create_commitment and ExtendShares + the DAH hash, which
+    run through the library; a caller without a device passes host functions.
+    DeviceSquares.process_blocks is compared against this function."""
+    from . import blobtx as btx, square as sq
+    from .shares import ShareError
+    none = _abi.BLOBTX_NONE
+    code_of = {n: i for i, n in enumerate(_abi.VERDICT_NAMES)}
+
+    def out(name, tx=none, word=0, aux=0):
+        return name == "ACCEPT", verdict_reason(code_of[name], tx, word, aux), (code_of[name], tx, word, aux)
+
+    if create_commitment is None:
+        from . import trees
+        create_commitment = trees.create_commitment
+    for idx, raw in enumerate(txs):
+        raw = bytes(raw)
+        kind, index = btx.check_tx(raw)
+        if kind:
+            name = "NON_BLOB_TX_HAS_PFB" if btx.KIND_NAMES[kind] == "NON_BLOB_TX_HAS_PFB" else "INVALID_BLOB_TX"
+            return out(name, idx, kind | index << 8)
+        t, is_blob_tx = btx.unmarshal_blob_tx(raw)
+        if not is_blob_tx:
+            continue
+        pfb = btx.pfb_of_tx(t.tx)
+        for i, declared in enumerate(pfb.share_commitments):
+            b = t.blobs[i]
+            try:
+                calculated = create_commitment(bytes([b.namespace_version]) + b.namespace_id, b.data)
+            except Exception:
+                return out("CALCULATE_COMMITMENT", idx, 0, i)
+            if bytes(calculated) != bytes(declared):
+                return out("INVALID_SHARE_COMMITMENT", idx, 0, i)
+    try:
+        square = sq.construct([bytes(t) for t in txs])
+    except ShareError:
+        return out("CONSTRUCT_FAILED")
+    if square_size is not None and int(square_size) != square.size():
+        return out("SQUARE_SIZE_DIFFERS", aux=square.size())
+    if data_hash is not None:
+        try:
+            root = (data_root or _data_root_of)(square.square_bytes())
+        except DAError:
+            return out("EXTEND_FAILED")
+        if bytes(root) != bytes(data_hash):
+            return out("DATA_ROOT_DIFFERS")
+    return out("ACCEPT")

@@ -726,6 +726,128 @@ def validate_blob_txs_device(planned: PlannedSquares, blob_base="plans", ctx: Op
     return tx_status[:ntx_total], block_status[:n], expected[:rows]
 
 
+class CommitPlan(NamedTuple):
+    """commit_plan_device's outputs, cuda tensors at capacity: the table image
+    (uint32 words, commit_layout's), the counts record {nblobs, nshares, nsub,
+    nwork, max_subtrees, 0, 0, 0} and blob_base (n + 1 int64)."""
+    tables: torch.Tensor
+    counts: torch.Tensor
+    blob_base: torch.Tensor
+
+
+def commit_plan_device(planned: PlannedSquares, k: int, threshold: int = 64, ctx: Optional[Context] = None,
+                       stream: Optional[torch.cuda.Stream] = None) -> CommitPlan:
+    """dagpu_commit_plan_device: the tables of the commitment check for the
+    blocks of width k, laid out on the device from the plans and records
+    plan_squares_device left in HBM.  Nothing is downloaded; enqueued on
+    `stream`."""
+    c = ctx or default_context()
+    n, dev = planned.n, planned.arena.device
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    L = c._L
+    with torch.cuda.stream(s):
+        tables = torch.empty((max(L.dagpu_commit_plan_table_words(k, n), 4),), dtype=torch.int32, device=dev)
+        counts = torch.zeros((_abi.COMMIT_COUNT_WORDS,), dtype=torch.int32, device=dev)
+        blob_base = torch.zeros((n + 1,), dtype=torch.int64, device=dev)
+        ws = torch.empty((max(L.dagpu_commit_plan_workspace_size(k, n), 16),), dtype=torch.uint8, device=dev)
+    rc = L.dagpu_commit_plan_device(c.handle, k, n, _abi.addr(planned.arena), planned.arena_cap,
+                                    _abi.addr(planned.records), threshold, _abi.addr(tables), _abi.addr(counts),
+                                    _abi.addr(blob_base), _abi.addr(ws), _stream_handle(s))
+    if rc != 0:
+        raise DAError(rc, c.last_error())
+    return CommitPlan(tables, counts, blob_base)
+
+
+class ProposalCheck(NamedTuple):
+    """proposal_check_device's outputs, cuda tensors.  The per-row tensors are
+    sized by the capacity n * k * k; rows [0, blob_base[n]) are meaningful."""
+    tx_status: torch.Tensor      # (ntx_total,) int32
+    block_status: torch.Tensor   # (n, 2) int32
+    expected: torch.Tensor       # (cap, 32) uint8
+    commitments: torch.Tensor    # (cap, 32) uint8
+    blob_status: torch.Tensor    # (cap,) int32
+    row_tx: torch.Tensor         # (cap, 2) int32: {tx in the block, blob in the tx} or -1
+    square_status: torch.Tensor  # (n,) int32
+    counts: torch.Tensor         # (8,) int32
+    blob_base: torch.Tensor      # (n + 1,) int64
+
+
+def proposal_check_device(planned: PlannedSquares, k: int, squares: torch.Tensor, square_stride: int,
+                          row_pitch: int, threshold: int = 64, ctx: Optional[Context] = None,
+                          stream: Optional[torch.cuda.Stream] = None) -> ProposalCheck:
+    """dagpu_proposal_check_device over what construct_squares_device left in
+    HBM: ValidateBlobTx's stateless rules, the commitment layout, the tie of
+    every plan blob to its declared commitment and the commitments of the
+    squares, compared on the device.  One enqueue on `stream`, no read."""
+    c = ctx or default_context()
+    n, dev = planned.n, planned.src.device
+    if planned.src_offs is None:
+        raise ValueError("planned carries no request: it must come from plan_squares_device")
+    ntx_total = int(planned.tx_lens.size)
+    cap = max(n * k * k, 1)
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    L = c._L
+    with torch.cuda.stream(s):
+        out = ProposalCheck(
+            torch.empty((max(ntx_total, 1),), dtype=torch.int32, device=dev),
+            torch.empty((max(n, 1), 2), dtype=torch.int32, device=dev),
+            torch.empty((cap, 32), dtype=torch.uint8, device=dev),
+            torch.empty((cap, 32), dtype=torch.uint8, device=dev),
+            torch.empty((cap,), dtype=torch.int32, device=dev),
+            torch.empty((cap, 2), dtype=torch.int32, device=dev),
+            torch.empty((max(n, 1),), dtype=torch.int32, device=dev),
+            torch.zeros((_abi.COMMIT_COUNT_WORDS,), dtype=torch.int32, device=dev),
+            torch.zeros((n + 1,), dtype=torch.int64, device=dev))
+        ws = torch.empty((max(L.dagpu_proposal_check_workspace_size(k, n, ntx_total), 16),), dtype=torch.uint8,
+                         device=dev)
+    rc = L.dagpu_proposal_check_device(
+        c.handle, k, n, _abi.addr(planned.src), _abi.addr(planned.src_offs), planned.src_bytes,
+        _abi.addr(planned.ntx), _abi.addr(planned.tx_lens) if ntx_total else None, _abi.addr(planned.arena),
+        planned.arena_cap, _abi.addr(planned.records), _abi.addr(squares), square_stride, row_pitch, threshold,
+        *(_abi.addr(t) for t in out), _abi.addr(ws), _stream_handle(s))
+    if rc != 0:
+        raise DAError(rc, c.last_error())
+    return out._replace(tx_status=out.tx_status[:ntx_total], block_status=out.block_status[:n],
+                        square_status=out.square_status[:n])
+
+
+def proposal_verdict_device(planned: PlannedSquares, k: int, check: ProposalCheck,
+                            extend_status: Optional[torch.Tensor] = None, dah: Optional[torch.Tensor] = None,
+                            data_hashes=None, square_sizes=None, ctx: Optional[Context] = None,
+                            stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+    """dagpu_proposal_verdict_device: (n, 4) int32 {code, tx, word, aux} per
+    block (_abi.VERDICT_NAMES) in ProcessProposal's order, from the planner's
+    records, proposal_check_device's outputs, extend's status and data roots,
+    and the proposed data_hashes ((n, 32) bytes) and square_sizes (n ints) on
+    the HOST, either of which may be None.  Enqueued on `stream`."""
+    import numpy as np
+    c = ctx or default_context()
+    n, dev = planned.n, planned.records.device
+    hashes = sizes = None
+    if data_hashes is not None:
+        hashes = np.frombuffer(b"".join(bytes(h) for h in data_hashes), np.uint8).copy()
+        if hashes.size != 32 * n:
+            raise ValueError("data_hashes holds 32 bytes per block")
+    if square_sizes is not None:
+        sizes = np.ascontiguousarray(np.asarray(square_sizes, dtype=np.uint32).reshape(-1))
+        if sizes.size != n:
+            raise ValueError("square_sizes holds one width per block")
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    L = c._L
+    with torch.cuda.stream(s):
+        verdicts = torch.empty((max(n, 1), 4), dtype=torch.int32, device=dev)
+        ws = torch.empty((max(L.dagpu_proposal_verdict_workspace_size(k, n, 0), 16),), dtype=torch.uint8, device=dev)
+    rc = L.dagpu_proposal_verdict_device(
+        c.handle, k, n, _abi.addr(planned.records), _abi.addr(check.block_status), _abi.addr(check.blob_status),
+        _abi.addr(check.row_tx), _abi.addr(check.blob_base),
+        _abi.addr(extend_status) if extend_status is not None else None, _abi.addr(dah) if dah is not None else None,
+        _abi.addr(hashes) if hashes is not None else None, _abi.addr(sizes) if sizes is not None else None,
+        _abi.addr(verdicts), _abi.addr(ws), _stream_handle(s))
+    if rc != 0:
+        raise DAError(rc, c.last_error())
+    return verdicts[:n]
+
+
 def construct_squares_device(k: int, blocks, out: torch.Tensor, square_stride: int, row_pitch: int,
                              max_square_size: int = 128, threshold: int = 64, ctx: Optional[Context] = None,
                              stream: Optional[torch.cuda.Stream] = None, threads: int = 16) -> PlannedSquares:
@@ -1186,6 +1308,52 @@ class DeviceSquares:
             else:
                 out.append((True, ""))
         return out
+
+    def process_blocks(self, blocks, data_hashes=None, square_sizes=None,
+                       stream: Optional[torch.cuda.Stream] = None, threads: int = 16):
+        """ProcessProposal's data-parallel part (app/process_proposal.go:53-164)
+        for n blocks of raw txs as upload, enqueue and one read: the planner and
+        the square writer (construct_squares_device, its status not read),
+        proposal_check_device, extend(), proposal_verdict_device, then one
+        .cpu() of the n x 4 verdict words.  Returns [(accept, reason)] with the
+        reference's log strings in the reference's order (da.verdict_reason;
+        da.process_proposal is the readable mirror); the raw records stay in
+        self.verdicts ((n, 4) uint32 {code, tx, word, aux}, _abi.VERDICT_NAMES)
+        and the check's tensors in self.proposal_check.  Nothing a proposer can
+        put into a block raises: a block the planner rejects, or one of
+        another width (NOT_JUDGED, never an accept), has its record.  The
+        plans stay in HBM for tx_table(), proof_store() and the other
+        follow-ups; nothing else is downloaded."""
+        import numpy as np
+
+        from . import da as _da, square as sq
+        if len(blocks) != self.n:
+            raise ValueError(f"{self.n} blocks expected, got {len(blocks)}")
+        if self.ods is None and not self.in_place:
+            raise ValueError("no ODS buffer: DeviceSquares(with_ods=False) takes its input through extend_from")
+        self._proof_store = self._tx_index = None
+        self._planned = self._validated = None
+        self._plans = self._src_lens = None
+        self._dah_ready = False
+        s = stream if stream is not None else torch.cuda.current_stream(self.eds.device)
+        w = 2 * self.k
+        out, stride, pitch = ((self.eds, w * w * 512, w * 512) if self.in_place
+                              else (self.ods, self.k * self.k * 512, self.k * 512))
+        p = construct_squares_device(self.k, blocks, out.view(-1), stride, pitch,
+                                     max_square_size=sq.SQUARE_SIZE_UPPER_BOUND, threshold=sq.SUBTREE_ROOT_THRESHOLD,
+                                     ctx=self.ctx, stream=s, threads=threads)
+        check = proposal_check_device(p, self.k, out.view(-1), stride, pitch, threshold=sq.SUBTREE_ROOT_THRESHOLD,
+                                      ctx=self.ctx, stream=s)
+        self.extend(stream=s)
+        verdicts = proposal_verdict_device(p, self.k, check, extend_status=self.status, dah=self.dah,
+                                           data_hashes=data_hashes, square_sizes=square_sizes, ctx=self.ctx, stream=s)
+        with torch.cuda.stream(s):
+            self.verdicts = verdicts.cpu().numpy().view(np.uint32)
+        self.proposal_check = check
+        self._plans = p
+        self._src_lens = p.src_lens
+        self._planned = p
+        return [(int(v[0]) == 0, _da.verdict_reason(*(int(x) for x in v))) for v in self.verdicts]
 
     # ---- square read (dagpu_square_scan_device / dagpu_square_read_device) ----
 

@@ -98,9 +98,8 @@ __device__ __forceinline__ void rfc_inner_hash(const uint32_t (&l)[8], const uin
 
 }  // namespace
 
-__global__ __launch_bounds__(256) void commit_leaf_kernel(CommitArgs a) {
-  const uint32_t g = blockIdx.x * 256u + threadIdx.x;
-  if (g >= a.nshares) return;
+// leaf record g of the batch
+__device__ __forceinline__ void commit_leaf_body(const CommitArgs& a, uint32_t g) {
   uint32_t lo = 0, hi = a.nblobs;  // share_pre[lo] <= g < share_pre[hi]
   while (hi - lo > 1) {
     const uint32_t mid = (lo + hi) >> 1;
@@ -120,8 +119,14 @@ __global__ __launch_bounds__(256) void commit_leaf_kernel(CommitArgs a) {
   o[5] = make_uint4(bswap32(st[4]), bswap32(st[5]), bswap32(st[6]), bswap32(st[7]));
 }
 
-__global__ __launch_bounds__(64) void commit_subtree_kernel(CommitArgs a) {
-  const uint32_t* q = a.sub + 3 * a.work[blockIdx.x];
+__global__ __launch_bounds__(256) void commit_leaf_kernel(CommitArgs a) {
+  const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+  if (g < a.nshares) commit_leaf_body(a, g);
+}
+
+// work item `item` by one wave; ends behind a workgroup barrier
+__device__ __forceinline__ void commit_subtree_body(const CommitArgs& a, uint32_t item) {
+  const uint32_t* q = a.sub + 3 * a.work[item];
   const uint32_t blob = q[0], first = q[1], size = q[2];
   // level L reads level L - 1: odd levels live in `inner`, even ones (the
   // leaves are level 0) in the leaf records, this subtree's window of each
@@ -164,8 +169,11 @@ __global__ __launch_bounds__(64) void commit_subtree_kernel(CommitArgs a) {
   if (bad) atomicOr(&a.status[blob], DAGPU_COMMIT_PUSH_ORDER);
 }
 
-__global__ __launch_bounds__(64) void commit_root_kernel(CommitArgs a) {
-  const uint32_t b = blockIdx.x, lane = threadIdx.x;
+__global__ __launch_bounds__(64) void commit_subtree_kernel(CommitArgs a) { commit_subtree_body(a, blockIdx.x); }
+
+// blob b by one wave
+__device__ __forceinline__ void commit_root_body(const CommitArgs& a, uint32_t b) {
+  const uint32_t lane = threadIdx.x;
   const uint32_t s0 = a.sub_pre[b], T = a.sub_pre[b + 1] - s0;
   uint8_t* d0 = a.dig0 + (uint64_t)s0 * 32;
   uint8_t* d1 = a.dig1 + (uint64_t)s0 * 32;
@@ -215,6 +223,47 @@ __global__ __launch_bounds__(64) void commit_root_kernel(CommitArgs a) {
   }
 }
 
+__global__ __launch_bounds__(64) void commit_root_kernel(CommitArgs a) { commit_root_body(a, blockIdx.x); }
+
+// ---- the counted forms (dagpu_proposal_check_device) ---------------------------------
+// The tables were laid out on the device (commit_plan.hip), so the host knows
+// neither the counts nor where each table starts inside the image: every
+// workgroup reads the counts record (uniform loads) and strides over the items.
+// The launch is sized by the capacity and a cap; a workgroup past the count
+// leaves at once.
+__device__ __forceinline__ CommitArgs commit_counted_args(const CommitCounted& c) {
+  CommitArgs a = c.a;
+  a.nblobs = c.counts[0];
+  a.nshares = c.counts[1];
+  a.nsub = c.counts[2];
+  a.nwork = c.counts[3];
+  const uint64_t o_share_pre = 2 * (uint64_t)a.nblobs, o_sub_pre = o_share_pre + a.nblobs + 1;
+  const uint64_t o_sub = o_sub_pre + a.nblobs + 1;
+  a.blob = c.tables;
+  a.share_pre = c.tables + o_share_pre;
+  a.sub_pre = c.tables + o_sub_pre;
+  a.sub = c.tables + o_sub;
+  a.work = c.tables + o_sub + 3 * (uint64_t)a.nsub;
+  return a;
+}
+
+__global__ __launch_bounds__(256) void commit_leaf_counted_kernel(CommitCounted c) {
+  const CommitArgs a = commit_counted_args(c);
+  for (uint64_t g = blockIdx.x * 256ull + threadIdx.x; g < a.nshares; g += gridDim.x * 256ull)
+    commit_leaf_body(a, (uint32_t)g);
+}
+
+// the loop bounds are uniform over the workgroup: the barriers inside the bodies are legal
+__global__ __launch_bounds__(64) void commit_subtree_counted_kernel(CommitCounted c) {
+  const CommitArgs a = commit_counted_args(c);
+  for (uint32_t i = blockIdx.x; i < a.nwork; i += gridDim.x) commit_subtree_body(a, i);
+}
+
+__global__ __launch_bounds__(64) void commit_root_counted_kernel(CommitCounted c) {
+  const CommitArgs a = commit_counted_args(c);
+  for (uint32_t b = blockIdx.x; b < a.nblobs; b += gridDim.x) commit_root_body(a, b);
+}
+
 hipError_t launch_commit_leaves(const CommitArgs& a, hipStream_t s) {
   if (a.nshares == 0) return hipSuccess;
   hipLaunchKernelGGL(commit_leaf_kernel, dim3((a.nshares + 255) / 256), dim3(256), 0, s, a);
@@ -230,6 +279,29 @@ hipError_t launch_commit_subtrees(const CommitArgs& a, hipStream_t s) {
 hipError_t launch_commit_roots(const CommitArgs& a, hipStream_t s) {
   if (a.nblobs == 0) return hipSuccess;
   hipLaunchKernelGGL(commit_root_kernel, dim3(a.nblobs), dim3(64), 0, s, a);
+  return hipGetLastError();
+}
+
+static unsigned counted_grid(uint64_t capacity_groups, uint32_t grid_cap) {
+  const uint64_t g = capacity_groups < grid_cap ? capacity_groups : grid_cap;
+  return (unsigned)(g ? g : 1);
+}
+
+hipError_t launch_commit_leaves_counted(const CommitCounted& c, uint64_t capacity, uint32_t grid_cap, hipStream_t s) {
+  if (capacity == 0) return hipSuccess;
+  hipLaunchKernelGGL(commit_leaf_counted_kernel, dim3(counted_grid((capacity + 255) / 256, grid_cap)), dim3(256), 0, s, c);
+  return hipGetLastError();
+}
+
+hipError_t launch_commit_subtrees_counted(const CommitCounted& c, uint64_t capacity, uint32_t grid_cap, hipStream_t s) {
+  if (capacity == 0) return hipSuccess;
+  hipLaunchKernelGGL(commit_subtree_counted_kernel, dim3(counted_grid(capacity, grid_cap)), dim3(64), 0, s, c);
+  return hipGetLastError();
+}
+
+hipError_t launch_commit_roots_counted(const CommitCounted& c, uint64_t capacity, uint32_t grid_cap, hipStream_t s) {
+  if (capacity == 0) return hipSuccess;
+  hipLaunchKernelGGL(commit_root_counted_kernel, dim3(counted_grid(capacity, grid_cap)), dim3(64), 0, s, c);
   return hipGetLastError();
 }
 

@@ -46,6 +46,18 @@ __global__ __launch_bounds__(256) void bt_tie(BtArgs a) {
   if (row < a.nrows) bt_tie_row(a, row);
 }
 
+// for dagpu_proposal_check_device (commit_plan_host.cpp)
+hipError_t launch_bt_validate(const BtArgs& a, hipStream_t s) {
+  if (a.ntx_total == 0) return hipSuccess;
+  hipLaunchKernelGGL(bt_validate, dim3((unsigned)((a.ntx_total + 255) / 256)), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+hipError_t launch_bt_finish(const BtArgs& a, hipStream_t s) {
+  if (a.n == 0) return hipSuccess;
+  hipLaunchKernelGGL(bt_finish, dim3((a.n + 255) / 256), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
 }  // namespace dagpu
 
 extern "C" {

@@ -538,7 +538,10 @@ DAGPU_SQ_HD inline void bt_finish_block(const BtArgs& a, uint32_t i) {
 // there (a walk of the one tx), and that blob's declared commitment.  Anything
 // that does not tie (a block without a plan, a row past the plan's blobs, a tx
 // that failed before its commitment lengths were checked) leaves zeros.
-DAGPU_SQ_HD inline void bt_tie_row(const BtArgs& a, uint64_t row) {
+// `owner` (null, or two words per row) receives the block-local index of the tx
+// that owns the blob and the blob's index inside that tx, or kBtNone twice for
+// a row that does not tie.
+DAGPU_SQ_HD inline void bt_tie_row(const BtArgs& a, uint64_t row, uint32_t* owner = nullptr) {
   uint32_t lo = 0, hi = a.n;  // the last block with blob_base <= row
   while (hi - lo > 1) {
     const uint32_t mid = lo + ((hi - lo) >> 1);
@@ -549,6 +552,7 @@ DAGPU_SQ_HD inline void bt_tie_row(const BtArgs& a, uint64_t row) {
   const SpRecord r = a.rec[lo];
   const uint64_t i = row - a.blob_base[lo];
   uint32_t from = kBtNone;  // of the 32 bytes, in src
+  uint32_t own_tx = kBtNone, own_blob = kBtNone;
   const uint8_t* src = a.src + b.src_off;
   do {
     if (r.plan_bytes < sizeof(SqHdr) || r.plan_off > a.arena_cap || r.plan_bytes > a.arena_cap - r.plan_off)
@@ -585,7 +589,13 @@ DAGPU_SQ_HD inline void bt_tie_row(const BtArgs& a, uint64_t row) {
     for (uint32_t q = 0; q <= j; q++) have = bt_bytes_next(tx + info.pfb_off, info.pfb_len, 4, ci, off, len);
     if (!have || len != kBtCommitment) break;
     from = t.off + info.pfb_off + off;
+    own_tx = tl;
+    own_blob = j;
   } while (false);
+  if (owner) {
+    owner[2 * row] = own_tx;
+    owner[2 * row + 1] = own_blob;
+  }
   uint8_t* out = a.expected + row * kBtCommitment;
   for (uint32_t q = 0; q < kBtCommitment; q++) out[q] = from == kBtNone ? (uint8_t)0 : src[from + q];
 }

@@ -148,6 +148,18 @@ struct CommitArgs {
 hipError_t launch_commit_leaves(const CommitArgs& a, hipStream_t s);
 hipError_t launch_commit_subtrees(const CommitArgs& a, hipStream_t s);
 hipError_t launch_commit_roots(const CommitArgs& a, hipStream_t s);
+// The counted forms: the tables are commit_plan.hip's image in device memory
+// and the counts record {nblobs, nshares, nsub, nwork, ...} lies beside it, so
+// `a` carries no table pointer and no count; the kernels stride over the items
+// on a grid of min(capacity, grid_cap) workgroups.
+struct CommitCounted {
+  CommitArgs a;
+  const uint32_t* tables;
+  const uint32_t* counts;
+};
+hipError_t launch_commit_leaves_counted(const CommitCounted& c, uint64_t capacity, uint32_t grid_cap, hipStream_t s);
+hipError_t launch_commit_subtrees_counted(const CommitCounted& c, uint64_t capacity, uint32_t grid_cap, hipStream_t s);
+hipError_t launch_commit_roots_counted(const CommitCounted& c, uint64_t capacity, uint32_t grid_cap, hipStream_t s);
 
 // Namespace search over the row trees of one square (nmt_namespace.hip;
 // arithmetic in ns_find.hpp).  One lane per (query, row).

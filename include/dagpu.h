@@ -1175,6 +1175,126 @@ int dagpu_blob_tx_validate_host(size_t n, const uint8_t* src, const size_t* src_
                                 const void* records, const uint64_t* blob_base, uint32_t* tx_status,
                                 uint32_t* block_status, uint8_t* expected);
 
+/* ---- ProcessProposal on the device: raw txs to verdicts in one read ---------
+ * The commitment check laid out where the plans lie, and the verdict of the
+ * data-parallel part of ProcessProposal (app/process_proposal.go:53-164) per
+ * block.  Arithmetic in csrc/commit_plan.hpp, shared by the kernels and the
+ * host executors.
+ *
+ * dagpu_commit_plan_device / dagpu_commit_plan_host: from the plan arena and
+ * SpRecord[n] dagpu_square_plan_device left (d_plans, plans_cap, d_records) to
+ * the tables dagpu_blob_commitments_device's kernels read, for the batch's
+ * width k and subtree_root_threshold, with no download:
+ *   d_tables    the image commit_layout builds from the same blobs, word for
+ *               word: blob[nblobs]{square, first_share} | share_pre[nblobs + 1]
+ *               | sub_pre[nblobs + 1] | sub[nsub]{blob, first leaf, size} |
+ *               work[nwork]; blocks in order, a block's blobs in plan order
+ *   d_counts    8 words {nblobs, nshares, nsub, nwork, max_subtrees, 0, 0, 0}
+ *   d_blob_base n + 1 uint64: block i owns rows [blob_base[i], blob_base[i + 1])
+ * A block contributes nothing when its record has a status, no plan
+ * (plan_bytes == 0) or another width than k, when an offset of its record or
+ * plan header passes plan_bytes or plans_cap (nothing outside is read), or when
+ * its blobs do not fit k * k shares.  Capacities need no read:
+ *   shares, rows, subtrees and blobs <= n * k * k;  work items <= n * k * k / 2;
+ *   d_tables holds dagpu_commit_plan_table_words(k, n) = 7.5 n k^2 + 2 words.
+ * k a power of two <= 1024 (else DAGPU_ERR_UNSUPPORTED), threshold > 0,
+ * n * k * k < 2^31, n < 2^24; d_plans, d_records, d_tables, d_counts 16-B and
+ * d_blob_base 8-B aligned.  Three kernels on `stream`, no copy and no wait with
+ * a workspace (dagpu_commit_plan_workspace_size(k, n) bytes, 16-B aligned);
+ * with NULL the library allocates it and waits.  The host executor runs the
+ * same functions as loops over host memory; no context, no device.
+ *
+ * dagpu_proposal_check_device: the request as dagpu_blob_tx_validate_device
+ * takes it (with its checks and messages) and the squares
+ * dagpu_square_construct_device wrote (d_squares, square_stride, row_pitch as
+ * in dagpu_blob_commitments_device).  Enqueues the per-tx rules (d_tx_status,
+ * d_block_status as there), the layout above, the tie of every row to its
+ * declared commitment and the three commitment kernels in their counted forms
+ * (grids of min(capacity, a fixed multiple of the CU count) workgroups striding
+ * over the counts the layout left in d_counts).  Outputs, all DEVICE, sized by capacity
+ * cap = n * k * k:
+ *   d_expected, d_commitments  cap x 32 B; rows [0, blob_base[n]) are written
+ *   d_blob_status   cap int32, DAGPU_COMMIT_* per row, zeroed up to cap first
+ *   d_row_tx        cap x 2 uint32: the block-local index of the tx that owns
+ *                   the row's blob and the blob's index inside that tx, or
+ *                   0xFFFFFFFF twice for a row that does not tie
+ *   d_square_status n int32, the OR over each block's rows, zeroed first
+ *   d_counts (8 words), d_blob_base (n + 1 uint64) as above
+ * No device-to-host copy; the call returns once its tables have left the
+ * context's page-locked staging.  d_workspace:
+ * dagpu_proposal_check_workspace_size(k, n, ntx_total) bytes, 16-B aligned,
+ * valid until the kernels have run; NULL: the library allocates and waits.
+ *
+ * dagpu_proposal_verdict_device / _host: four uint32 per block {code, tx, word,
+ * aux} from the records, the check's outputs, extend's per-square status and
+ * data roots (d_extend_status, d_dah; may be NULL) and two HOST arrays that may
+ * be NULL: data_hashes (n x 32) and square_sizes (n uint32), uploaded on
+ * `stream` through the context's page-locked staging.  The first code that
+ * applies, in the reference's order:
+ *   NON_BLOB_TX_HAS_PFB (:75) / INVALID_BLOB_TX (:120)  the lowest failing tx of
+ *       the loop fails a stateless rule; tx, word = its DAGPU_BLOBTX_* word
+ *   CALCULATE_COMMITMENT / INVALID_SHARE_COMMITMENT (:120, blob_tx.go:91-100)
+ *       the lowest failing tx fails on a commitment (DAGPU_COMMIT_PUSH_ORDER /
+ *       _MISMATCH); tx, aux = the blob's index in the tx.  The tx reported is
+ *       the lowest over both rule sets; a tx that fails both ways reports the
+ *       stateless word, as ValidateBlobTx does; within a tx the lowest blob,
+ *       its push-order fault before its mismatch.
+ *   CONSTRUCT_FAILED (:135-139)  the planner rejected the block; word = its
+ *       status.  No square was written for such a block, so a commitment
+ *       mismatch in it cannot be seen: its code is its lowest stateless failure
+ *       if it has one, else this one.  It is rejected either way.
+ *   SQUARE_SIZE_DIFFERS (:142-145)  square_sizes given and != the block's
+ *       width; aux = the computed width
+ *   NOT_JUDGED  the block's width is not k: no square was written, nothing was
+ *       compared; the caller sends the block to a batch of its width.  Never
+ *       an accept.
+ *   EXTEND_FAILED (:147-157), DATA_ROOT_DIFFERS (:161-164), ACCEPT.
+ * Two kernels: one lane per row with a status folds its key into its block's
+ * word (64-bit atomic min), one lane per block writes the record.  d_workspace:
+ * dagpu_proposal_verdict_workspace_size(k, n, ntx_total) bytes.  Refusals of
+ * all three calls (null pointers, misalignment, k, threshold, pitch) return
+ * DAGPU_ERR_ARG / DAGPU_ERR_UNSUPPORTED with a message before anything is
+ * enqueued; no output byte is touched. */
+#define DAGPU_VERDICT_ACCEPT 0
+#define DAGPU_VERDICT_NON_BLOB_TX_HAS_PFB 1
+#define DAGPU_VERDICT_INVALID_BLOB_TX 2
+#define DAGPU_VERDICT_CALCULATE_COMMITMENT 3
+#define DAGPU_VERDICT_INVALID_SHARE_COMMITMENT 4
+#define DAGPU_VERDICT_CONSTRUCT_FAILED 5
+#define DAGPU_VERDICT_SQUARE_SIZE_DIFFERS 6
+#define DAGPU_VERDICT_NOT_JUDGED 7
+#define DAGPU_VERDICT_EXTEND_FAILED 8
+#define DAGPU_VERDICT_DATA_ROOT_DIFFERS 9
+size_t dagpu_commit_plan_table_words(uint32_t k, size_t n);
+size_t dagpu_commit_plan_workspace_size(uint32_t k, size_t n);
+int dagpu_commit_plan_device(dagpu_ctx* ctx, uint32_t k, size_t n, const uint8_t* d_plans, size_t plans_cap,
+                             const void* d_records, uint32_t subtree_root_threshold, uint32_t* d_tables,
+                             uint32_t* d_counts, uint64_t* d_blob_base, void* d_workspace, void* stream);
+int dagpu_commit_plan_host(uint32_t k, size_t n, const uint8_t* plans, size_t plans_cap, const void* records,
+                           uint32_t subtree_root_threshold, uint32_t* tables, uint32_t* counts, uint64_t* blob_base);
+size_t dagpu_proposal_check_workspace_size(uint32_t k, size_t n, size_t ntx_total);
+int dagpu_proposal_check_device(dagpu_ctx* ctx, uint32_t k, size_t n, const uint8_t* d_src, const size_t* src_offs,
+                                size_t src_bytes, const uint32_t* ntx, const uint64_t* tx_lens,
+                                const uint8_t* d_plans, size_t plans_cap, const void* d_records,
+                                const uint8_t* d_squares, size_t square_stride, size_t row_pitch,
+                                uint32_t subtree_root_threshold, uint32_t* d_tx_status, uint32_t* d_block_status,
+                                uint8_t* d_expected, uint8_t* d_commitments, int32_t* d_blob_status,
+                                uint32_t* d_row_tx, int32_t* d_square_status, uint32_t* d_counts,
+                                uint64_t* d_blob_base, void* d_workspace, void* stream);
+size_t dagpu_proposal_verdict_workspace_size(uint32_t k, size_t n, size_t ntx_total);
+int dagpu_proposal_verdict_device(dagpu_ctx* ctx, uint32_t k, size_t n, const void* d_records,
+                                  const uint32_t* d_block_status, const int32_t* d_blob_status,
+                                  const uint32_t* d_row_tx, const uint64_t* d_blob_base,
+                                  const int32_t* d_extend_status /* may be NULL */,
+                                  const uint8_t* d_dah /* may be NULL */,
+                                  const uint8_t* data_hashes /* HOST, may be NULL */,
+                                  const uint32_t* square_sizes /* HOST, may be NULL */, uint32_t* d_verdicts,
+                                  void* d_workspace, void* stream);
+int dagpu_proposal_verdict_host(uint32_t k, size_t n, const void* records, const uint32_t* block_status,
+                                const int32_t* blob_status, const uint32_t* row_tx, const uint64_t* blob_base,
+                                const int32_t* extend_status, const uint8_t* dah, const uint8_t* data_hashes,
+                                const uint32_t* square_sizes, uint32_t* verdicts);
+
 /* ---- Square read: txs and blobs back out of squares resident in HBM -------
  * The opposite direction of dagpu_square_write_device: square.Deconstruct
  * (pkg/square/square.go:65-155) split into a scan of the shares
