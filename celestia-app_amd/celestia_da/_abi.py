@@ -94,6 +94,14 @@ EXPORTS = (
     "dagpu_proposal_verdict_workspace_size",
     "dagpu_proposal_verdict_device",
     "dagpu_proposal_verdict_host",
+    "dagpu_secp256k1_verify_device",
+    "dagpu_secp256k1_verify_host",
+    "dagpu_secp256k1_g_table",
+    "dagpu_tx_sig_verify_workspace_size",
+    "dagpu_tx_signers_device",
+    "dagpu_tx_signers_host",
+    "dagpu_tx_sig_verify_device",
+    "dagpu_tx_sig_verify_host",
     "dagpu_square_scan_workspace_size",
     "dagpu_square_scan_device",
     "dagpu_square_scan_host",
@@ -165,6 +173,17 @@ VERDICT_NAMES = ("ACCEPT", "NON_BLOB_TX_HAS_PFB", "INVALID_BLOB_TX", "CALCULATE_
                  "INVALID_SHARE_COMMITMENT", "CONSTRUCT_FAILED", "SQUARE_SIZE_DIFFERS", "NOT_JUDGED", "EXTEND_FAILED",
                  "DATA_ROOT_DIFFERS")
 COMMIT_COUNT_WORDS = 8
+# dagpu_secp256k1_verify_* / dagpu_tx_sig_verify_*: status word = kind | index << 8 (DAGPU_SIG_*);
+# kinds 1 .. 5 are not judged, kinds from 16 on reject
+SIG_KIND_NAMES = {
+    0: "SIG_OK", 1: "SIG_TX_UNDECODABLE", 2: "SIG_UNSUPPORTED_SIGNERS", 3: "SIG_UNSUPPORTED_MODE",
+    4: "SIG_UNSUPPORTED_PUBKEY_TYPE", 5: "SIG_NO_PUBKEY", 16: "SIG_BAD_PUBKEY", 17: "SIG_BAD_LENGTH",
+    18: "SIG_OUT_OF_RANGE", 19: "SIG_HIGH_S", 20: "SIG_MISMATCH"}
+SIG_KINDS = {name: kind for kind, name in SIG_KIND_NAMES.items()}
+SIG_REJECTING = 16
+SIG_RECORD_BYTES = 136
+SIGNER_RECORD_BYTES = 48
+SIG_NONE = 0xFFFFFFFF
 # dagpu_square_scan_device / dagpu_square_read_device (include/dagpu.h)
 SCAN_OK, SCAN_NAMESPACE, SCAN_INCONSISTENT, SCAN_LENGTH, SCAN_OVERFLOW = 0, 1, 2, 3, 4
 SCAN_SUMMARY_WORDS = 8
@@ -329,6 +348,15 @@ def lib() -> ctypes.CDLL:
         L.dagpu_proposal_verdict_workspace_size.restype = sz
         L.dagpu_proposal_verdict_device.argtypes = [vp, u32, sz] + [vp] * 12
         L.dagpu_proposal_verdict_host.argtypes = [u32, sz] + [vp] * 10
+        L.dagpu_secp256k1_verify_device.argtypes = [vp, sz, vp, vp, vp, vp, vp]
+        L.dagpu_secp256k1_verify_host.argtypes = [sz, vp, vp, vp, vp]
+        L.dagpu_secp256k1_g_table.argtypes = [vp, ctypes.c_int]
+        L.dagpu_tx_sig_verify_workspace_size.argtypes = [sz, sz]
+        L.dagpu_tx_sig_verify_workspace_size.restype = sz
+        L.dagpu_tx_signers_device.argtypes = [vp, sz, vp, vp, sz, vp, vp, vp, vp, vp]
+        L.dagpu_tx_signers_host.argtypes = [sz, vp, vp, sz, vp, vp, vp]
+        L.dagpu_tx_sig_verify_device.argtypes = [vp, sz, vp, vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp]
+        L.dagpu_tx_sig_verify_host.argtypes = [sz, vp, vp, sz, vp, vp, vp, sz, vp, vp, vp, vp, vp]
         L.dagpu_square_scan_workspace_size.argtypes = [u32, sz]
         L.dagpu_square_scan_workspace_size.restype = sz
         L.dagpu_square_scan_device.argtypes = [vp, u32, sz, vp, sz, sz, u32, vp, vp, vp, vp, vp]

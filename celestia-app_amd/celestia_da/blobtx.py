@@ -575,3 +575,154 @@ def check_native(raw: bytes) -> Tuple[int, int]:
     buf = np.frombuffer(bytes(raw), np.uint8)
     word = _abi.lib().dagpu_blob_tx_check(_abi.addr(buf) if buf.size else None, buf.size)
     return word & 0xFF, word >> 8
+
+
+# ---- tx signatures: SIGN_MODE_DIRECT over secp256k1 (cosmos-sdk v0.46 x/auth/ante/sigverify.go) --------
+# The readable mirror of csrc/tx_sig.hpp, written independently of it (the curve is secp256k1.py).
+#   TxRaw      {bytes body_bytes = 1; bytes auth_info_bytes = 2; repeated bytes signatures = 3;}
+#   AuthInfo   {repeated SignerInfo signer_infos = 1; Fee fee = 2;}
+#   SignerInfo {Any public_key = 1; ModeInfo mode_info = 2; uint64 sequence = 3;}
+#   ModeInfo   {oneof sum {Single single = 1 {SignMode mode = 1;}; Multi multi = 2;}}
+#   SignDoc    {bytes body_bytes = 1; bytes auth_info_bytes = 2; string chain_id = 3; uint64 account_number = 4;}
+# A word is (kind, index), kind a key of _abi.SIG_KIND_NAMES (include/dagpu.h DAGPU_SIG_*).
+
+URL_SECP256K1_PUBKEY = "/cosmos.crypto.secp256k1.PubKey"
+SIGN_MODE_DIRECT = 1
+_SIG_CAP = (1 << 24) - 1
+
+
+def _wrap(num: int, v: bytes) -> bytes:
+    """A length-delimited field that is written even when empty."""
+    return _key(num, 2) + put_uvarint(len(v)) + v
+
+
+def marshal_signer_info(pubkey: Optional[bytes], sequence: int, mode: int = SIGN_MODE_DIRECT,
+                        type_url: str = URL_SECP256K1_PUBKEY, multi: bool = False) -> bytes:
+    out = b""
+    if pubkey is not None:
+        out += _wrap(1, _bytes_field(1, type_url.encode()) + _bytes_field(2, _bytes_field(1, bytes(pubkey))))
+    mode_info = _wrap(2, b"") if multi else _wrap(1, _varint_field(1, mode))
+    return out + _wrap(2, mode_info) + _varint_field(3, sequence)
+
+
+def marshal_auth_info(pubkey: Optional[bytes], sequence: int, mode: int = SIGN_MODE_DIRECT,
+                      type_url: str = URL_SECP256K1_PUBKEY, multi: bool = False, signers: int = 1,
+                      fee: bytes = b"") -> bytes:
+    """AuthInfo with `signers` copies of one SignerInfo (pubkey None: no
+    public_key; multi: ModeInfo.Multi) and an opaque fee."""
+    si = marshal_signer_info(pubkey, sequence, mode, type_url, multi)
+    return b"".join(_wrap(1, si) for _ in range(signers)) + _bytes_field(2, fee)
+
+
+def _inner_tx(raw: bytes) -> bytes:
+    t, is_blob = unmarshal_blob_tx(bytes(raw))
+    return t.tx if is_blob else bytes(raw)
+
+
+def _tx_raw(inner: bytes):
+    body, auth, sigs = b"", b"", []
+    for num, wt, v in _fields(inner):
+        if num == 1:
+            _want(wt, 2, "BodyBytes"); body = bytes(v)
+        elif num == 2:
+            _want(wt, 2, "AuthInfoBytes"); auth = bytes(v)
+        elif num == 3:
+            _want(wt, 2, "Signatures"); sigs.append(bytes(v))
+    return body, auth, sigs
+
+
+def sign_doc_bytes(tx: bytes, chain_id, account_number: int) -> bytes:
+    """DirectSignBytes of a tx (a BlobTx: of its inner tx): the SignDoc over
+    the exact body_bytes and auth_info_bytes ranges; empty and zero fields
+    are omitted."""
+    body, auth, _ = _tx_raw(_inner_tx(tx))
+    chain = chain_id.encode() if isinstance(chain_id, str) else bytes(chain_id)
+    return _bytes_field(1, body) + _bytes_field(2, auth) + _bytes_field(3, chain) + _varint_field(4, account_number)
+
+
+def _walk_signer(raw: bytes):
+    """(kind, index, key or None, sequence, signature) as the walk alone
+    classifies a tx: no table, no curve arithmetic."""
+    inner = _inner_tx(raw)
+    try:
+        _, auth, sigs = _tx_raw(inner)
+        sdk_tx_messages(inner)
+        infos = []
+        for num, wt, v in _fields(auth):
+            if num == 1:
+                _want(wt, 2, "SignerInfos"); infos.append(bytes(v))
+        if len(infos) != 1 or len(sigs) != 1:
+            return 2, min(len(infos), _SIG_CAP), None, 0, b""
+        any_, mode_info, sequence = None, b"", 0
+        for num, wt, v in _fields(infos[0]):
+            if num == 1:
+                _want(wt, 2, "PublicKey"); any_ = bytes(v)
+            elif num == 2:
+                _want(wt, 2, "ModeInfo"); mode_info = bytes(v)
+            elif num == 3:
+                _want(wt, 0, "Sequence"); sequence = v
+        which, single, mode = 0, b"", 0
+        for num, wt, v in _fields(mode_info):
+            if num in (1, 2):
+                _want(wt, 2, "Sum"); which = num
+                if num == 1:
+                    single = bytes(v)
+        if which == 1:
+            for num, wt, v in _fields(single):
+                if num == 1:
+                    _want(wt, 0, "Mode"); mode = v & 0xFFFFFFFF
+        url, value = b"", b""
+        if any_ is not None:
+            for num, wt, v in _fields(any_):
+                if num == 1:
+                    _want(wt, 2, "TypeUrl"); url = bytes(v)
+                elif num == 2:
+                    _want(wt, 2, "Value"); value = bytes(v)
+        if which != 1:
+            return 3, 0, None, sequence, sigs[0]
+        if mode != SIGN_MODE_DIRECT:
+            return 3, min(mode, _SIG_CAP), None, sequence, sigs[0]
+        key = None
+        if any_ is not None:
+            if url != URL_SECP256K1_PUBKEY.encode():
+                return 4, 0, None, sequence, sigs[0]
+            key = b""
+            for num, wt, v in _fields(value):
+                if num == 1:
+                    _want(wt, 2, "Key"); key = bytes(v)
+    except ProtoError:
+        return 1, 0, None, 0, b""
+    if key is None:
+        return 5, 0, None, sequence, sigs[0]
+    if len(key) != 33:
+        return 16, 0, key, sequence, sigs[0]
+    if len(sigs[0]) != 64:
+        return 17, min(len(sigs[0]), _SIG_CAP), key, sequence, sigs[0]
+    return 0, 0, key, sequence, sigs[0]
+
+
+def signer_of_tx(tx: bytes) -> Tuple[bytes, int, int]:
+    """(pubkey, kind, sequence) as dagpu_tx_signers_* records them: the 33-byte
+    key the tx carries (33 zeros when it carries none of that length), the
+    kind the walk alone gives, the sequence it declares."""
+    kind, _, key, sequence, _ = _walk_signer(bytes(tx))
+    return (key if key is not None and len(key) == 33 else bytes(33)), kind, sequence
+
+
+def check_signature(tx: bytes, chain_id, account_number: int, pubkey: Optional[bytes] = None) -> Tuple[int, int]:
+    """(kind, index) of one tx as dagpu_tx_sig_verify_* gives it.  pubkey: the
+    account's stored key (33 bytes), used instead of the tx's own when given."""
+    from . import _abi, secp256k1 as ec
+    tx = bytes(tx)
+    kind, index, key, _, sig = _walk_signer(tx)
+    if 1 <= kind <= 4:
+        return kind, index
+    if pubkey is not None:
+        key = bytes(pubkey)
+    elif kind in (5, 16):
+        return kind, index
+    if ec.decompress(key) is None:
+        return 16, 0
+    if len(sig) != 64:
+        return 17, min(len(sig), _SIG_CAP)
+    return _abi.SIG_KINDS[ec.verify(key, sign_doc_bytes(tx, chain_id, account_number), sig)], 0

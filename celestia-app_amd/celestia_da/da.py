@@ -559,7 +559,11 @@ def process_proposal(txs: Sequence[bytes], data_hash: Optional[bytes] = None, sq
     the comparison of every declared commitment with create_commitment
     (blob_tx.go:91-100); the first failing tx rejects.  Then square.construct
     (:135), the proposed square size (:142) and the data root (:147-164).
-    Signatures, the ante handler and upgrade messages are not checked.
+    Signatures, the ante handler and upgrade messages are not checked here:
+    the stateless half of the signature check (one secp256k1 verification over
+    SHA-256(SignDoc) per tx) is a call of its own beside this one,
+    DeviceSquares.verify_signatures / device.verify_tx_signatures_device
+    (mirror: blobtx.check_signature); the stateful ante rules stay with the caller.
     create_commitment(namespace, data) and data_root(list of share bytes)
     default to trees.create_commitment and ExtendShares + the DAH hash, which
     run through the library; a caller without a device passes host functions.

@@ -726,6 +726,114 @@ def validate_blob_txs_device(planned: PlannedSquares, blob_base="plans", ctx: Op
     return tx_status[:ntx_total], block_status[:n], expected[:rows]
 
 
+def secp256k1_verify_device(digests: torch.Tensor, sigs: torch.Tensor, pubkeys: torch.Tensor,
+                            ctx: Optional[Context] = None, stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+    """dagpu_secp256k1_verify_device: n secp256k1 ECDSA verifications, one lane
+    each.  digests (n, 32), sigs (n, 64; big-endian r | s) and pubkeys (n, 33;
+    compressed) are contiguous cuda uint8 tensors.  Returns the (n,) int32
+    status words (_abi.SIG_KIND_NAMES: 0, or BAD_PUBKEY, OUT_OF_RANGE, HIGH_S,
+    MISMATCH), enqueued on `stream`: it does not synchronise."""
+    c = ctx or default_context()
+    n = int(digests.shape[0]) if digests.dim() else 0
+    for t, width, name in ((digests, 32, "digests"), (sigs, 64, "sigs"), (pubkeys, 33, "pubkeys")):
+        if t.dtype != torch.uint8 or not t.is_cuda or not t.is_contiguous() or tuple(t.shape) != (n, width):
+            raise ValueError(f"{name} must be a contiguous cuda uint8 tensor of shape (n, {width})")
+    dev = digests.device
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.stream(s):
+        status = torch.empty((max(n, 1),), dtype=torch.int32, device=dev)
+    rc = c._L.dagpu_secp256k1_verify_device(c.handle, n, _abi.addr(digests), _abi.addr(sigs), _abi.addr(pubkeys),
+                                            _abi.addr(status), _stream_handle(s))
+    if rc != 0:
+        raise DAError(rc, c.last_error())
+    return status[:n]
+
+
+def tx_signers_device(planned: PlannedSquares, ctx: Optional[Context] = None,
+                      stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+    """dagpu_tx_signers_device over the txs plan_squares_device left in HBM:
+    the (ntx_total, 48) uint8 signer records {pubkey[33], kind, pad[6],
+    sequence u64}: the key each tx carries and the sequence it declares, for
+    the host's account lookup, nonce comparison and address check.  Enqueued on
+    `stream`."""
+    c = ctx or default_context()
+    n, dev = planned.n, planned.src.device
+    if planned.src_offs is None:
+        raise ValueError("planned carries no request: it must come from plan_squares_device")
+    ntx_total = int(planned.tx_lens.size)
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+    with torch.cuda.stream(s):
+        signers = torch.empty((max(ntx_total, 1), _abi.SIGNER_RECORD_BYTES), dtype=torch.uint8, device=dev)
+        ws = torch.empty((max(c._L.dagpu_tx_sig_verify_workspace_size(n, ntx_total), 16),), dtype=torch.uint8,
+                         device=dev)
+    rc = c._L.dagpu_tx_signers_device(
+        c.handle, n, _abi.addr(planned.src), _abi.addr(planned.src_offs), planned.src_bytes, _abi.addr(planned.ntx),
+        _abi.addr(planned.tx_lens) if ntx_total else None, _abi.addr(signers), _abi.addr(ws), _stream_handle(s))
+    if rc != 0:
+        raise DAError(rc, c.last_error())
+    return signers[:ntx_total]
+
+
+def verify_tx_signatures_device(planned: PlannedSquares, chain_id, account_numbers, pubkeys=None,
+                                ctx: Optional[Context] = None, stream: Optional[torch.cuda.Stream] = None,
+                                workspace: Optional[torch.Tensor] = None):
+    """dagpu_tx_sig_verify_device over the txs plan_squares_device left in HBM:
+    the stateless half of the SigVerificationDecorator, one secp256k1 ECDSA
+    verification over SHA-256(SignDoc) per tx (SIGN_MODE_DIRECT, one signer).
+
+    chain_id: str or bytes, at most 64 bytes.  account_numbers: (ntx_total,)
+    uint64-like, one per tx in batch order (a cuda int64 tensor is taken as it
+    is, anything else is uploaded).  pubkeys: None, or (ntx_total, 33) uint8:
+    the accounts' stored keys; a row whose first byte is 0 means none, a
+    present row is used instead of the key the tx carries.
+    Returns cuda tensors (tx_status (ntx_total,) int32, block_status (n, 4)
+    int32 {lowest tx with a rejecting kind or -1, its word, number of
+    not-judged txs, 0}, signers (ntx_total, 48) uint8); a word is kind |
+    index << 8 (_abi.SIG_KIND_NAMES; blobtx.check_signature is the mirror).
+    Enqueued on `stream`: it does not synchronise."""
+    import numpy as np
+    c = ctx or default_context()
+    n, dev = planned.n, planned.src.device
+    if planned.src_offs is None:
+        raise ValueError("planned carries no request: it must come from plan_squares_device")
+    ntx_total = int(planned.tx_lens.size)
+    chain = chain_id.encode() if isinstance(chain_id, str) else bytes(chain_id)
+    chain_buf = np.frombuffer(chain, np.uint8).copy()
+    s = stream if stream is not None else torch.cuda.current_stream(dev)
+
+    def table(v, dtype, shape, name):
+        if isinstance(v, torch.Tensor) and v.is_cuda:
+            if v.dtype != dtype or not v.is_contiguous() or tuple(v.shape) != shape:
+                raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {shape}")
+            return v
+        a = np.ascontiguousarray(v.cpu().numpy() if isinstance(v, torch.Tensor) else v,
+                                 np.uint64 if dtype == torch.int64 else np.uint8)
+        if a.shape != shape:
+            raise ValueError(f"{name} must have shape {shape}")
+        a = a.view(np.int64) if dtype == torch.int64 else a
+        return torch.from_numpy(a.copy()).to(dev, non_blocking=False)
+
+    with torch.cuda.stream(s):
+        accts = table(account_numbers, torch.int64, (ntx_total,), "account_numbers")
+        keys = None if pubkeys is None else table(pubkeys, torch.uint8, (ntx_total, 33), "pubkeys")
+        tx_status = torch.empty((max(ntx_total, 1),), dtype=torch.int32, device=dev)
+        block_status = torch.empty((max(n, 1), 4), dtype=torch.int32, device=dev)
+        signers = torch.empty((max(ntx_total, 1), _abi.SIGNER_RECORD_BYTES), dtype=torch.uint8, device=dev)
+        need = max(c._L.dagpu_tx_sig_verify_workspace_size(n, ntx_total), 16)
+        if workspace is None:
+            workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+        elif workspace.dtype != torch.uint8 or not workspace.is_cuda or workspace.numel() < need:
+            raise ValueError(f"workspace must be a cuda uint8 tensor of at least {need} bytes")
+    rc = c._L.dagpu_tx_sig_verify_device(
+        c.handle, n, _abi.addr(planned.src), _abi.addr(planned.src_offs), planned.src_bytes, _abi.addr(planned.ntx),
+        _abi.addr(planned.tx_lens) if ntx_total else None, _abi.addr(chain_buf) if chain_buf.size else None,
+        chain_buf.size, _abi.addr(accts) if ntx_total else None, _abi.addr(keys), _abi.addr(tx_status),
+        _abi.addr(block_status), _abi.addr(signers), _abi.addr(workspace), _stream_handle(s))
+    if rc != 0:
+        raise DAError(rc, c.last_error())
+    return tx_status[:ntx_total], block_status[:n], signers[:ntx_total]
+
+
 class CommitPlan(NamedTuple):
     """commit_plan_device's outputs, cuda tensors at capacity: the table image
     (uint32 words, commit_layout's), the counts record {nblobs, nshares, nsub,
@@ -1258,6 +1366,20 @@ class DeviceSquares:
                              "the host-plan route uploads no raw txs the device could walk")
         self._validated = validate_blob_txs_device(self._planned, ctx=self.ctx, stream=stream)
         return self._validated
+
+    def verify_signatures(self, chain_id, account_numbers, pubkeys=None,
+                          stream: Optional[torch.cuda.Stream] = None):
+        """The tx signatures of the batch load_txs(plan="device") or
+        process_blocks left in HBM: verify_tx_signatures_device's (tx_status,
+        block_status, signers), enqueued on `stream`.  account_numbers (and
+        pubkeys, the accounts' stored keys) hold one entry per tx in batch
+        order.  It reads the raw txs only: the squares, the verdicts and
+        every other result of the batch stay as they are."""
+        if self._planned is None:
+            raise ValueError("the txs are not resident in HBM: verify_signatures follows load_txs(plan='device') "
+                             "or process_blocks")
+        return verify_tx_signatures_device(self._planned, chain_id, account_numbers, pubkeys=pubkeys, ctx=self.ctx,
+                                           stream=stream)
 
     def process_proposals(self, data_hashes=None, stream: Optional[torch.cuda.Stream] = None):
         """The data-parallel part of ProcessProposal (app/process_proposal.go:53-164)

@@ -1295,6 +1295,116 @@ int dagpu_proposal_verdict_host(uint32_t k, size_t n, const void* records, const
                                 const int32_t* extend_status, const uint8_t* dah, const uint8_t* data_hashes,
                                 const uint32_t* square_sizes, uint32_t* verdicts);
 
+/* ---- Tx signatures: batched secp256k1 ECDSA, SIGN_MODE_DIRECT ---------------
+ * The stateless half of the SigVerificationDecorator (app/ante/ante.go:55,
+ * reached from app/process_proposal.go:103 and :126): one secp256k1 ECDSA
+ * verification over SHA-256(SignDoc) per tx, as cosmos-sdk v0.46
+ * crypto/keys/secp256k1 PubKey.VerifySignature makes it.  The stateful inputs
+ * (account numbers, stored public keys) come in as tables; the sequence
+ * comparison, the account lookup, the key-to-address check, fees and gas stay
+ * with the caller, who gets the signer records for them.  Arithmetic in
+ * csrc/secp256k1.hpp and csrc/tx_sig.hpp, shared by the kernels
+ * (csrc/tx_sig.hip) and the host executors (csrc/tx_sig_host.cpp).
+ *
+ * A status word is kind | index << 8.  0 is DAGPU_SIG_OK.  Not judged (the
+ * caller's host path decides these; none is a rejection):
+ *   TX_UNDECODABLE      the walk Tx -> AuthInfo -> SignerInfo -> Any / ModeInfo
+ *                       fails, the body's messages included
+ *                       (process_proposal.go:60-66 skips such a tx).  The walker
+ *                       is this project's (unknown fields skipped, the last of
+ *                       a field wins); the SDK's stricter canonical-encoding
+ *                       rejections are not restated.
+ *   UNSUPPORTED_SIGNERS signer_infos or signatures count != 1; index = the
+ *                       signer_infos count, capped at 2^24 - 1
+ *   UNSUPPORTED_MODE    not Single {SIGN_MODE_DIRECT}; index = the mode, 0 for
+ *                       Multi or none
+ *   UNSUPPORTED_PUBKEY_TYPE  a public_key whose type_url is not
+ *                       /cosmos.crypto.secp256k1.PubKey
+ *   NO_PUBKEY           none in the tx and none in the table
+ * Rejecting, checked in this order (the reference reports every one of them as
+ * ErrUnauthorized, so the order is this project's own):
+ *   BAD_PUBKEY          key length != 33, prefix not 0x02 / 0x03, x >= p, or
+ *                       x^3 + 7 not a square
+ *   BAD_LENGTH          signature length != 64; index = the length, capped
+ *   OUT_OF_RANGE        r = 0, r >= n or s = 0
+ *   HIGH_S              s > n / 2 (malleable)
+ *   MISMATCH            with z = SHA-256(sign bytes), w = 1 / s mod n:
+ *                       R = (z w) G + (r w) Q is infinity, or R.x mod n != r
+ *
+ * dagpu_secp256k1_verify_device / _host: the generic batch: n digests (32 B
+ * each), signatures (64 B, big-endian r | s) and compressed keys (33 B); one
+ * word per item, 0 or BAD_PUBKEY, OUT_OF_RANGE, HIGH_S, MISMATCH.  One kernel
+ * on `stream`, one lane per item, no copy and no wait.
+ *
+ * dagpu_secp256k1_g_table: the 15 affine multiples 1 G .. 15 G the
+ * verification adds by 4-bit window, 64 bytes each (big-endian x | y): the
+ * committed constants (recompute = 0), or computed by the library's own point
+ * arithmetic (recompute = 1); the tests compare both with the Python mirror.
+ *
+ * dagpu_tx_signers_device / _host: the request as dagpu_blob_tx_validate_device
+ * takes it (d_src, HOST src_offs[n + 1], src_bytes, HOST ntx[n], HOST tx_lens)
+ * with its request checks and messages.  d_signers (8-B aligned), 48 bytes per
+ * tx of the batch: {pubkey[33], kind u8, pad[6], sequence u64 little-endian}:
+ * the key the tx carries (zeros when it carries none of 33 bytes), the kind
+ * the walk alone gives (no table: NO_PUBKEY says the tx carries no key; kinds
+ * up to BAD_LENGTH), and the sequence it declares (0 for TX_UNDECODABLE and
+ * UNSUPPORTED_SIGNERS).  A BlobTx is unwrapped to its inner tx first.
+ *
+ * dagpu_tx_sig_verify_device / _host: the same request plus chain_id (HOST
+ * bytes, chain_id_len <= 64 or DAGPU_ERR_ARG), d_account_numbers (one uint64
+ * per tx of the batch, 8-B aligned) and d_pubkeys (may be NULL; ntx_total x
+ * 33; a row whose first byte is 0 means none; a present row is the key used,
+ * whatever key the tx carries, as the account's stored key is in the
+ * reference).  The sign bytes are the proto3 encoding of SignDoc {body_bytes 1,
+ * auth_info_bytes 2, chain_id 3, account_number 4} with body_bytes and
+ * auth_info_bytes the exact byte ranges of the tx's fields 1 and 2, a field
+ * omitted when empty or 0; they are streamed into SHA-256, never materialised.
+ * Outputs, all DEVICE:
+ *   d_tx_status     one word per tx of the batch, in batch order
+ *   d_block_status  four words per block: {index in the block of its lowest tx
+ *                   with a rejecting kind, or 0xFFFFFFFF; that tx's word, or
+ *                   0; the number of not-judged txs; 0}
+ *   d_signers       as above
+ * Three kernels on `stream`: one lane per tx (walk, hash), one lane per tx
+ * (curve arithmetic; a tx whose word is final leaves at once), one per block.
+ * d_workspace (16-B aligned, dagpu_tx_sig_verify_workspace_size(n, ntx_total)
+ * = 44 n + 152 ntx_total + 96 bytes at most) must stay valid until the kernels
+ * have run; the call returns once its tables have left host memory and does
+ * not wait for the kernels.  With NULL the library allocates it and waits.
+ * The host executors run the same functions as loops; no context, no device. */
+#define DAGPU_SIG_OK 0
+#define DAGPU_SIG_TX_UNDECODABLE 1
+#define DAGPU_SIG_UNSUPPORTED_SIGNERS 2
+#define DAGPU_SIG_UNSUPPORTED_MODE 3
+#define DAGPU_SIG_UNSUPPORTED_PUBKEY_TYPE 4
+#define DAGPU_SIG_NO_PUBKEY 5
+#define DAGPU_SIG_BAD_PUBKEY 16
+#define DAGPU_SIG_BAD_LENGTH 17
+#define DAGPU_SIG_OUT_OF_RANGE 18
+#define DAGPU_SIG_HIGH_S 19
+#define DAGPU_SIG_MISMATCH 20
+int dagpu_secp256k1_verify_device(dagpu_ctx* ctx, size_t n, const uint8_t* d_digests, const uint8_t* d_sigs,
+                                  const uint8_t* d_pubkeys, uint32_t* d_status, void* stream);
+int dagpu_secp256k1_verify_host(size_t n, const uint8_t* digests, const uint8_t* sigs, const uint8_t* pubkeys,
+                                uint32_t* status);
+int dagpu_secp256k1_g_table(uint8_t* out /* 15 x 64 */, int recompute);
+size_t dagpu_tx_sig_verify_workspace_size(size_t n, size_t ntx_total);
+int dagpu_tx_signers_device(dagpu_ctx* ctx, size_t n, const uint8_t* d_src, const size_t* src_offs, size_t src_bytes,
+                            const uint32_t* ntx, const uint64_t* tx_lens, uint8_t* d_signers, void* d_workspace,
+                            void* stream);
+int dagpu_tx_signers_host(size_t n, const uint8_t* src, const size_t* src_offs, size_t src_bytes, const uint32_t* ntx,
+                          const uint64_t* tx_lens, uint8_t* signers);
+int dagpu_tx_sig_verify_device(dagpu_ctx* ctx, size_t n, const uint8_t* d_src, const size_t* src_offs,
+                               size_t src_bytes, const uint32_t* ntx, const uint64_t* tx_lens,
+                               const uint8_t* chain_id /* HOST */, size_t chain_id_len,
+                               const uint64_t* d_account_numbers, const uint8_t* d_pubkeys /* may be NULL */,
+                               uint32_t* d_tx_status, uint32_t* d_block_status, uint8_t* d_signers,
+                               void* d_workspace, void* stream);
+int dagpu_tx_sig_verify_host(size_t n, const uint8_t* src, const size_t* src_offs, size_t src_bytes,
+                             const uint32_t* ntx, const uint64_t* tx_lens, const uint8_t* chain_id,
+                             size_t chain_id_len, const uint64_t* account_numbers, const uint8_t* pubkeys,
+                             uint32_t* tx_status, uint32_t* block_status, uint8_t* signers);
+
 /* ---- Square read: txs and blobs back out of squares resident in HBM -------
  * The opposite direction of dagpu_square_write_device: square.Deconstruct
  * (pkg/square/square.go:65-155) split into a scan of the shares
